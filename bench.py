@@ -31,10 +31,20 @@ never imports torch (round 5): the barriers around the timed region, the max ove
 abundances are collectives of the library's own RCCL communicator, whose unique id travels from rank 0 to the others
 through a unix socket of their own (class Star).
 
-At N = 1 the cfg3 line also carries `text_to_abundances` (--no-text skips it): the same reads written as two Themisto
-plaintext strands and taken from text to abundances.txt -- the reader on the device (msw_alignment_read_device), the
-likelihood build from its device-resident classes, the solve to --tol 1e-6 -- with the host reader on the same files
+A plain run (no --full) does only what the headline needs: set-up, a short clock warm-up, the W warm-up steps, ONE
+timed region of exactly K steps (`ms_per_step` = its time / K), the outputs if --dump-outputs is given, the line.
+Everything else the line can carry is behind --full: the convergence solves and the EM legs before the timed region,
+the median of five repeats of the K-step region, the profiled run with the per-kernel and roofline figures, the
+bootstrap_cfg4 leg, time_to_first_theta, text_to_abundances and the CPU baselines.
+
+With --full at N = 1 the cfg3 line also carries `text_to_abundances` (--no-text skips it): the same reads written as two
+Themisto plaintext strands and taken from text to abundances.txt -- the reader on the device (msw_alignment_read_device),
+the likelihood build from its device-resident classes, the solve to --tol 1e-6 -- with the host reader on the same files
 beside it; `--config e2e` is the long form of that leg (Python mirror and gzip pair included).
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64): `theta` (the
+abundances; every replicate's with N > 1 or cfg4) and `bound` (the ELBO of the last iteration; cfg4: `iters`, the
+iterations per replicate).  The inputs are generated from the seed, so two builds compare output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -59,6 +69,7 @@ TRAFFIC_JSON = {"cfg3": ["r05_traffic_pmc.json", "r04_traffic_pmc.json", "r03_tr
                 "cfg3-diverse": ["r05_diverse_traffic_pmc.json", "r04_diverse_traffic_pmc.json", "r03_diverse_traffic_pmc.json"],
                 "cfg4-diverse": ["r05_diverse_traffic_pmc.json", "r04_diverse_traffic_pmc.json", "r03_diverse_traffic_pmc.json"]}
 N_CU, N_SE, SIMD_PER_CU = 256, 32, 4   # MI355X: 8 XCDs x 32 CUs, 4 shader engines per XCD (the SQ_BUSY_CYCLES instances)
+CLOCK_WARMUP_S = 0.3   # plain run: seconds of sweeps before the W warm-up steps (a cold chip needs 40-80 ms to reach its clocks)
 
 
 def pmc_bound(entry):
@@ -113,6 +124,12 @@ def parse():
                          "column sums every iteration (strong scaling)")
     ap.add_argument("--force-dist", action="store_true",
                     help="create the RCCL communicator even with one rank (exercises the N > 1 code path)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: convergence solves and EM legs, five repeats of the "
+                         "timed region, per-kernel and roofline figures, bootstrap_cfg4, time_to_first_theta, "
+                         "text_to_abundances, CPU baselines (--no-extras / --no-text / --no-cpu-baseline trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     a = ap.parse_args()
     dflt = {"cfg2": (1_000_000, 500, 1), "cfg3": (10_000_000, 5000, 2), "cfg4": (10_000_000, 5000, 2),
             "cfg5": (50_000_000, 20_000, 3), "e2e": (10_000_000, 5000, 2)}[a.config]
@@ -604,6 +621,7 @@ def run_e2e(a):
         core.set_pack_schedule(False)   # one solve: the drivers skip the bank ordering below five bootstrap replicates
         stages = {}
         best = None
+        outputs = {}
         def one_pass(device_reader):
             t1 = time.perf_counter()
             if device_reader:
@@ -627,6 +645,7 @@ def run_e2e(a):
             with open(os.path.join(tmp, "e2e_abundances.txt"), "w") as f:
                 f.write(out.getvalue())
             t5 = time.perf_counter()
+            outputs.update(theta=res["theta"], bound=[res["bound"]])
             cur = {"read_collapse_s": t2 - t1, "build_likelihood_s": t3 - t2, "solve_s": t4 - t3, "write_abundances_s": t5 - t4,
                    "total_s": t5 - t1, "iters": int(res["iters"]), "ecs": int(n_ecs), "target_hits": int(n_hits)}
             # (a few ECs fewer than the generator made: the reference keys reads by a 64-bit XOR-shift hash of their
@@ -646,6 +665,8 @@ def run_e2e(a):
                     best = cur
             both[device_reader] = (best, text)
         assert both[False][1] == both[True][1], "abundances.txt differs between the host and the device reader"
+        if a.dump_outputs:   # the solve of the device reader's last pass
+            dump_outputs(a.dump_outputs, outputs)
         stages, stages_host = both[True][0], both[False][0]
         threads = int(os.environ.get("MSWEEP_READER_THREADS", "0")) or min(16, cpu_share())
         # the Python mirror of the reference's reader on a prefix of the same files
@@ -955,7 +976,24 @@ def bootstrap_leg(core, comm, w, per_rank, world, G):
     dt = time.perf_counter() - t0
     bt = core.last_bootstrap_timing()
     assert theta.shape == (B, G) and np.all(np.abs(theta.sum(1) - 1.0) < 1e-9)
-    return dt, iters, bt
+    return dt, iters, bt, theta
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays (name -> array) as path/<name>.npy in float64; beyond DUMP_LIMIT bytes in all, every array is cut to the same
+    fixed, seeded sample of its flattened elements (ascending indices)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT:
+            k = max(v.size * DUMP_LIMIT // total, 1)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def iteration_histogram(iters):
@@ -1071,9 +1109,9 @@ def main():
     # 60-80 ms of activity (tools/timing.py ramp: the SAME twenty iterations take 0.214 ms each on a cold chip,
     # 0.181 ms once it has been busy for 40 ms), and the timed region is to measure the path, not the governor.
     conv = em = em_float = None
-    prewarm = {"ms": 0.0, "what": "none (--no-prewarm)"}
+    prewarm = {"ms": 0.0, "what": "none (--no-prewarm)" if a.full else "none (plain run)"}
     t_pre = time.perf_counter()
-    if not shard and not a.no_extras:
+    if a.full and not shard and not a.no_extras:
         runs = []
         for _ in range(2 + int(os.environ.get("MSWEEP_BENCH_PRESOLVES", "0"))):  # developer switch: more of them
             t1 = time.perf_counter()
@@ -1124,9 +1162,10 @@ def main():
         bootstrap_leg(core, boot_comm, w, max(a.warmup, 1), world, G)   # W untimed replicates per rank (builds the
         sync()                                                          # cumulative table, opens RCCL's connections)
         t0 = time.perf_counter()
-        dt_call, iters, bt = bootstrap_leg(core, boot_comm, w, a.steps, world, G)
+        dt_call, iters, bt, theta = bootstrap_leg(core, boot_comm, w, a.steps, world, G)
         sync()
         dt = time.perf_counter() - t0
+        outputs = {"theta": theta, "iters": iters}
         steps_total = a.steps * world
         tot_iters = int(iters.sum())
         cells = float(E) * G * tot_iters
@@ -1137,27 +1176,41 @@ def main():
                       "iters_per_sec": tot_iters / dt, "listed_cells_per_sec": float(nnz) * tot_iters / dt,
                       "reads_x_groups_cells_per_sec": float(wl["reads"]) * G * tot_iters / dt}
         # per-kernel durations for the roofline object: a fixed-iteration solve with events, as for cfg3
-        core.prepare(logc, alpha0)
-        core.set_fixed_iters(True)
-        core.set_profiling(True)
-        core.run(max_iters=20)
-        core.continue_(100)
-        tm = core.last_timing()
-        tm0 = None
-        core.set_profiling(False)
+        if a.full:
+            core.prepare(logc, alpha0)
+            core.set_fixed_iters(True)
+            core.set_profiling(True)
+            core.run(max_iters=20)
+            core.continue_(100)
+            tm = core.last_timing()
+            core.set_profiling(False)
     else:
         core.set_fixed_iters(True)
         if conv is None:
             core.prepare(logc, alpha0)           # inputs resident in HBM before the timed region
         # (after the convergence run they already are: msw_core_solve = msw_core_prepare + msw_core_run)
+        if not a.full and not shard:
+            # a plain run has no convergence solves to bring the clocks up (see above), and the first K-step region after
+            # other work runs ~1.5 % slower than the ones after it (the first of --full's five repeats): the region's own
+            # calls -- W warm-up steps, then K (at most 1000) -- again and again for CLOCK_WARMUP_S instead, untimed.
+            n_pre, t_pre = 0, time.perf_counter()
+            while time.perf_counter() - t_pre < CLOCK_WARMUP_S:
+                core.run(max_iters=max(a.warmup, 1))
+                core.continue_(min(a.steps, 1000))
+                n_pre += 1
+            prewarm = {"ms": (time.perf_counter() - t_pre) * 1e3,
+                       "what": f"{n_pre} untimed passes of the W warm-up steps + min(K, 1000) steps of the timed solve "
+                               "(clocks up), host wall clock, before the W warm-up steps; --full runs the convergence "
+                               "solves and the EM leg here instead"}
         # W untimed warm-up steps: the first W iterations of the solve (with its set-up: the evaluation of the
         # initial state and the first iteration's rejected step); the K timed steps are the NEXT K iterations of
         # the same solve (msw_core_continue) -- every kernel slot they need, rejected steps included
         # The timed region is a few milliseconds at the driver's K = 20 (one scheduler hiccup on the host moves it by
         # several per cent): it is taken REPEATS times -- every time the W warm-up iterations again (untimed), then the
         # same K iterations, barrier + synchronisation on both sides, max over ranks -- and the MEDIAN is the line's
-        # ms_per_step / value; all of them are in ms_per_step_runs.
-        REPEATS = 5
+        # ms_per_step / value; all of them are in ms_per_step_runs.  A plain run times the K steps once: --steps is
+        # then the number of steps timed.
+        REPEATS = 5 if a.full else 1
         dts, dev = [], []
         for rep in range(REPEATS):
             core.run(max_iters=max(a.warmup, 1))
@@ -1166,9 +1219,11 @@ def main():
             sync()
             t0 = time.perf_counter()
             res = core.continue_(a.steps)         # exactly K steps
+            outputs = {"theta": res["theta"], "bound": [res["bound"]]}
             if multi and not shard:
                 gathered = comm.allgather(res["theta"])   # (world, G): the per-replicate abundances, RCCL all-gather
                 assert gathered.shape == (world, G)
+                outputs["theta"] = gathered
             sync()
             dts.append(max_over_ranks(time.perf_counter() - t0))
             tm0 = core.last_timing()
@@ -1179,21 +1234,24 @@ def main():
         # K more steps with HIP events around every sweep launch (on the solve stream) for the
         # per-kernel durations of the roofline object.  Kept out of the timed run: every event record
         # is a barrier packet that costs ~6 us of idle GPU between two kernels.
-        core.set_profiling(True)
-        core.run(max_iters=max(a.warmup, 1))      # the same iterations as the timed ones: W, then K
-        core.continue_(a.steps)
-        tm = core.last_timing()
-        core.set_profiling(False)
+        if a.full:
+            core.set_profiling(True)
+            core.run(max_iters=max(a.warmup, 1))      # the same iterations as the timed ones: W, then K
+            core.continue_(a.steps)
+            tm = core.last_timing()
+            core.set_profiling(False)
         mult = 1 if shard else n_gpus
         cells = float(E) * G * a.steps * mult
         line_extra = {"iters_per_sec": a.steps * mult / dt, "listed_cells_per_sec": float(nnz) * a.steps * mult / dt,
                       "reads_x_groups_cells_per_sec": float(wl["reads"]) * G * a.steps * mult / dt,
                       "device_ms_per_step": float(np.median(dev)),
                       "ms_per_step_runs": [x * 1e3 / a.steps for x in dts],
-                      "ms_per_step_what": f"median of {REPEATS} repeats of the K-step region (each: W untimed warm-up "
-                                          "iterations, barrier + synchronisation, K timed iterations, synchronisation + barrier; "
-                                          "max over ranks per repeat)"}
-        if shard:
+                      "ms_per_step_what": (f"median of {REPEATS} repeats of the K-step region (each: W untimed warm-up "
+                                           "iterations, barrier + synchronisation, K timed iterations, synchronisation + "
+                                           "barrier; max over ranks per repeat)") if a.full else
+                                          ("the K-step region once (W untimed warm-up iterations, barrier + synchronisation, "
+                                           "K timed iterations, synchronisation + barrier; max over ranks)")}
+        if shard and a.full:
             # where an iteration of the EC-sharded solve goes on rank 0 (the profiled run: events around the sweeps and
             # around the two all-reduces with their packing kernels): the first hardware run says which part to fix
             it = max(tm["iters"], 1)
@@ -1208,16 +1266,18 @@ def main():
                         "k_finstep, k_redfin (redundant on every rank) and the launch boundaries"}
     if a.config == "cfg4":
         dt = max_over_ranks(dt)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, outputs)
 
     # the real replicate loop beside every cfg3 line: msw_core_bootstrap_dist, fixed replicates per rank
     boot = None
-    if a.config == "cfg3" and not shard and not a.no_extras and a.bootstrap_per_rank > 0:
+    if a.full and a.config == "cfg3" and not shard and not a.no_extras and a.bootstrap_per_rank > 0:
         core.set_fixed_iters(False)
         w = wl["w"]
         bootstrap_leg(core, boot_comm, w, 1, world, G)      # not timed: cumulative table, connections, clones
         sync()
         t1 = time.perf_counter()
-        _, iters, bt = bootstrap_leg(core, boot_comm, w, a.bootstrap_per_rank, world, G)
+        _, iters, bt, _ = bootstrap_leg(core, boot_comm, w, a.bootstrap_per_rank, world, G)
         sync()
         tb = time.perf_counter() - t1
         tb = max_over_ranks(tb)
@@ -1229,45 +1289,7 @@ def main():
                         "mt19937_64 stream, resamples and solves its replicates to --tol 1e-6, ONE all-gather of the "
                         "B x (G + 1) table; max over ranks of the host wall clock, barrier on both sides"}
 
-    # the practical ceiling beside the specification: the rates this very device reaches with a
-    # read-only 16-byte-load sweep and with the triad -- on a buffer the size of the sweeps' record stream (what
-    # a kernel that does nothing but read that stream once would get, launch ramp and tail included) and on 4 GiB
     if rank == 0:
-        stream_read, stream_triad = core.hbm_stream_rates(max(int(tm["bytes_passB"]), 1 << 20), 5)
-        stream_read_4g, stream_triad_4g = core.hbm_stream_rates(1 << 32, 3)
-        msA = tm["passA_ms"] / max(tm["passA_launches"], 1)
-        msB = tm["passB_ms"] / max(tm["passB_launches"], 1)
-        dom, ms_dom, b_dom = ("k_passB", msB, tm["bytes_passB"]) if msB >= msA else ("k_passA", msA, tm["bytes_passA"])
-        achieved = b_dom / (ms_dom * 1e-3) / 1e9 if ms_dom > 0 else 0.0
-        # HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE),
-        # collected offline on this exact workload and committed under profiles/
-        traffic, traffic_src, busy = None, None, None
-        if a.default_shape:
-            tkey = a.config + ("-diverse" if a.group_sizes == "diverse" else "")
-            if a.config == "cfg2" and os.environ.get("MSWEEP_DENSE_COMPRESS") == "0":
-                tkey = "cfg2-dense"
-            for name in TRAFFIC_JSON.get(tkey, []):
-                try:
-                    tj = json.load(open(os.path.join(ROOT, "profiles", name)))
-                    ent = next(v for k, v in tj.items() if dom[2:] in k)     # ("passB": k_passB<..>, k_dense_passB<..>)
-                    traffic = ent["hbm_bytes_per_launch"]
-                    busy = pmc_bound(ent)
-                    traffic_src = f"profiles/{name} (offline rocprofv3 --pmc passes on this workload, not this run)"
-                    break
-                except Exception:
-                    continue
-        # what bounds the dominant kernel: the record stream is NOT it where the counters say that LDS (gathers, integer
-        # atomics, half of the cycles bank conflicts) and VALU issue are both busy and overlap only in part
-        bound = "hbm"
-        if busy is not None:
-            lb, vb = busy["lds_busy_frac"], busy["valu_busy_frac"]
-            if vb >= 0.75 and lb < 0.3:
-                bound = "valu (hbm frac reported)"          # the dense sweeps: one fp64 exp per cell
-            elif lb >= 0.75 and vb < 0.3:
-                bound = "lds (hbm frac reported)"
-            elif max(lb, vb) >= 0.4:
-                bound = "lds+valu (hbm frac reported)"
-        gb = lambda b, ms: b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
         sharding = "single solve" if n_gpus == 1 else (
             f"one solve, ECs sharded over {n_gpus} GPUs, {os.environ.get('MSWEEP_ALLREDUCE', 'rccl')} all-reduce of 1 double and "
             "of 3 G integers + 4 doubles per iteration" if shard else
@@ -1287,27 +1309,66 @@ def main():
                             "listed_cells_per_sec counts the cells the CSR-of-ECs form stores (nnz per iteration)",
             "rccl_ranks": rccl_ranks,
             "prewarm": prewarm,
-            "kernels": {"k_passA_ms": msA, "k_passB_ms": msB, "passA_launches": tm["passA_launches"],
-                        "passB_launches": tm["passB_launches"]},
-            "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "lds_busy_frac": busy and busy["lds_busy_frac"], "lds_conflict_frac": busy and busy["lds_conflict_frac"],
-                         "valu_busy_frac": busy and busy["valu_busy_frac"],
-                         "bound_what": "achieved / peak / frac are ALGORITHMIC bytes of the kernel's record stream against the "
-                                       "HBM peak, as the contract asks; lds_busy / valu_busy / lds_conflict are the kernel's "
-                                       "SQ counters from the same committed PMC file as `traffic`: LDS-array cycles and VALU "
-                                       "issue cycles as fractions of the kernel's duration, conflict cycles as a fraction "
-                                       "of the LDS cycles (bench.py pmc_bound)",
-                         "algorithmic_bytes_per_launch": b_dom, "avg_launch_ms": ms_dom,
-                         "measured_stream_GBs": {"read_only_same_size": stream_read, "triad_same_size": stream_triad,
-                                                 "read_only_4GiB": stream_read_4g, "triad_4GiB": stream_triad_4g,
-                                                 "what": "msw_core_hbm_stream_rates on this device, best of 7 shapes x "
-                                                         "5 launches; same_size = a buffer of algorithmic_bytes_per_launch"},
-                         "frac_of_measured_read": achieved / stream_read if stream_read else None,
-                         "kernels": {"k_passA": {"achieved": gb(tm["bytes_passA"], msA), "frac": gb(tm["bytes_passA"], msA) / HBM_PEAK_GBS},
-                                     "k_passB": {"achieved": gb(tm["bytes_passB"], msB), "frac": gb(tm["bytes_passB"], msB) / HBM_PEAK_GBS}}},
             "setup_s": wl["setup_s"],
         }
+        if a.full:
+            # the practical ceiling beside the specification: the rates this very device reaches with a
+            # read-only 16-byte-load sweep and with the triad -- on a buffer the size of the sweeps' record stream (what
+            # a kernel that does nothing but read that stream once would get, launch ramp and tail included) and on 4 GiB
+            stream_read, stream_triad = core.hbm_stream_rates(max(int(tm["bytes_passB"]), 1 << 20), 5)
+            stream_read_4g, stream_triad_4g = core.hbm_stream_rates(1 << 32, 3)
+            msA = tm["passA_ms"] / max(tm["passA_launches"], 1)
+            msB = tm["passB_ms"] / max(tm["passB_launches"], 1)
+            dom, ms_dom, b_dom = ("k_passB", msB, tm["bytes_passB"]) if msB >= msA else ("k_passA", msA, tm["bytes_passA"])
+            achieved = b_dom / (ms_dom * 1e-3) / 1e9 if ms_dom > 0 else 0.0
+            # HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE),
+            # collected offline on this exact workload and committed under profiles/
+            traffic, traffic_src, busy = None, None, None
+            if a.default_shape:
+                tkey = a.config + ("-diverse" if a.group_sizes == "diverse" else "")
+                if a.config == "cfg2" and os.environ.get("MSWEEP_DENSE_COMPRESS") == "0":
+                    tkey = "cfg2-dense"
+                for name in TRAFFIC_JSON.get(tkey, []):
+                    try:
+                        tj = json.load(open(os.path.join(ROOT, "profiles", name)))
+                        ent = next(v for k, v in tj.items() if dom[2:] in k)     # ("passB": k_passB<..>, k_dense_passB<..>)
+                        traffic = ent["hbm_bytes_per_launch"]
+                        busy = pmc_bound(ent)
+                        traffic_src = f"profiles/{name} (offline rocprofv3 --pmc passes on this workload, not this run)"
+                        break
+                    except Exception:
+                        continue
+            # what bounds the dominant kernel: the record stream is NOT it where the counters say that LDS (gathers, integer
+            # atomics, half of the cycles bank conflicts) and VALU issue are both busy and overlap only in part
+            bound = "hbm"
+            if busy is not None:
+                lb, vb = busy["lds_busy_frac"], busy["valu_busy_frac"]
+                if vb >= 0.75 and lb < 0.3:
+                    bound = "valu (hbm frac reported)"          # the dense sweeps: one fp64 exp per cell
+                elif lb >= 0.75 and vb < 0.3:
+                    bound = "lds (hbm frac reported)"
+                elif max(lb, vb) >= 0.4:
+                    bound = "lds+valu (hbm frac reported)"
+            gb = lambda b, ms: b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            line["kernels"] = {"k_passA_ms": msA, "k_passB_ms": msB, "passA_launches": tm["passA_launches"],
+                               "passB_launches": tm["passB_launches"]}
+            line["roofline"] = {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                                "lds_busy_frac": busy and busy["lds_busy_frac"], "lds_conflict_frac": busy and busy["lds_conflict_frac"],
+                                "valu_busy_frac": busy and busy["valu_busy_frac"],
+                                "bound_what": "achieved / peak / frac are ALGORITHMIC bytes of the kernel's record stream against the "
+                                              "HBM peak, as the contract asks; lds_busy / valu_busy / lds_conflict are the kernel's "
+                                              "SQ counters from the same committed PMC file as `traffic`: LDS-array cycles and VALU "
+                                              "issue cycles as fractions of the kernel's duration, conflict cycles as a fraction "
+                                              "of the LDS cycles (bench.py pmc_bound)",
+                                "algorithmic_bytes_per_launch": b_dom, "avg_launch_ms": ms_dom,
+                                "measured_stream_GBs": {"read_only_same_size": stream_read, "triad_same_size": stream_triad,
+                                                        "read_only_4GiB": stream_read_4g, "triad_4GiB": stream_triad_4g,
+                                                        "what": "msw_core_hbm_stream_rates on this device, best of 7 shapes x "
+                                                                "5 launches; same_size = a buffer of algorithmic_bytes_per_launch"},
+                                "frac_of_measured_read": achieved / stream_read if stream_read else None,
+                                "kernels": {"k_passA": {"achieved": gb(tm["bytes_passA"], msA), "frac": gb(tm["bytes_passA"], msA) / HBM_PEAK_GBS},
+                                            "k_passB": {"achieved": gb(tm["bytes_passB"], msB), "frac": gb(tm["bytes_passB"], msB) / HBM_PEAK_GBS}}}
         try:
             line["layout"] = core.layout_info()
         except Exception:
@@ -1317,12 +1378,12 @@ def main():
             line["likelihood_build"] = wl["build"]
         if conv is not None:
             line["time_to_convergence"] = conv
-        if wl.get("first_theta") is not None and n_gpus == 1 and not a.no_extras:
+        if a.full and wl.get("first_theta") is not None and n_gpus == 1 and not a.no_extras:
             try:
                 line["time_to_first_theta"] = wl["first_theta"]()
             except Exception as ex:  # reporting only
                 line["time_to_first_theta"] = {"ms": None, "what": f"failed: {ex}"}
-        if wl.get("from_text") is not None and n_gpus == 1 and not a.no_extras and not a.no_text:
+        if a.full and wl.get("from_text") is not None and n_gpus == 1 and not a.no_extras and not a.no_text:
             log("text -> abundances ...")
             try:
                 line["text_to_abundances"] = wl["from_text"]()
@@ -1334,7 +1395,7 @@ def main():
             line["em_algorithm_float"] = em_float
         if boot is not None:
             line["bootstrap_cfg4"] = boot
-        if not a.no_cpu_baseline and n_gpus == 1:   # rank 0 at N = 1 only: the host cores are shared by the ranks
+        if a.full and not a.no_cpu_baseline and n_gpus == 1:   # rank 0 at N = 1 only: the host cores are shared by the ranks
             log("cpu baseline ...")
             try:
                 line.update(wl["cpu"]())

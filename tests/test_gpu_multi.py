@@ -97,8 +97,8 @@ def test_bench_with_two_ranks_on_one_gpu(mode, transport):
     import json
     env = dict(os.environ, MSWEEP_BENCH_ONE_GPU="1", MSWEEP_ALLREDUCE=transport, GPU_MAX_HW_QUEUES="8",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-           "--reads", "300000", "--groups", "300", "--mode", mode]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
+           "--no-cpu-baseline", "--reads", "300000", "--groups", "300", "--mode", mode]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
@@ -124,7 +124,7 @@ def test_bench_under_torchrun_with_two_ranks_on_one_gpu():
     env.update(MSWEEP_BENCH_ONE_GPU="1", GPU_MAX_HW_QUEUES="8", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--no-cpu-baseline", "--reads", "300000", "--groups", "300"]
+           "--full", "--no-cpu-baseline", "--reads", "300000", "--groups", "300"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")][-1])

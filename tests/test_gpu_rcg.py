@@ -721,6 +721,44 @@ def test_continue_is_the_same_solve(gpu_core):
         gpu_core.continue_(3)
 
 
+def test_plain_bench_run_dumps_what_its_timed_steps_computed(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the headline line alone, and theta / bound after the W warm-up and
+    the K timed steps -- what the same fixed-iteration solve gives in this process, and the same bits in a second run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    R, G, W, K = 200_000, 300, 3, 7
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads", str(R), "--groups", str(G),
+                            "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0 and line["value"] > 0
+        assert (line["unit"], line["higher_is_better"], line["dtype"]) == ("cells/s", True, "f64")
+        assert len(line["ms_per_step_runs"]) == 1
+        for extra in ("kernels", "roofline", "time_to_convergence", "em_algorithm", "bootstrap_cfg4", "time_to_first_theta",
+                      "text_to_abundances", "cpu_baseline"):
+            assert extra not in line, extra
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("theta", "bound")})
+    for n in ("theta", "bound"):
+        assert dumps[0][n].dtype == np.float64
+        np.testing.assert_array_equal(dumps[1][n], dumps[0][n])
+    assert dumps[0]["theta"].shape == (G,) and abs(dumps[0]["theta"].sum() - 1.0) < 1e-9
+    p = synth.make_csr_problem(R, G, seed=2)      # bench.py's cfg3 generator at its default seed
+    with Core(0) as c:
+        lik = from_grouped_counts(c, p["rowptr"], p["grp"], p["cnt"], p["ec_counts"], p["group_sizes"])
+        c.set_fixed_iters(True)
+        c.prepare(lik.log_counts(), np.ones(G))
+        ref = c.run(max_iters=W + K)
+    np.testing.assert_allclose(dumps[0]["theta"], ref["theta"], rtol=1e-12, atol=1e-300)
+    np.testing.assert_allclose(dumps[0]["bound"], [ref["bound"]], rtol=1e-12)
+
+
 def test_gamma_block_equals_the_columns_of_gamma(gpu_core, oracle):
     """msw_core_gamma_block: any block of ECs of the log-responsibility matrix (what --write-probs and the
     binning input read EC by EC, src/Sample.cpp:63-85), CSR and dense flavours; blocks tile the matrix."""

@@ -171,3 +171,28 @@ def test_bench_launcher_fails_fast_when_a_rank_dies():
     r = _bench(["--gpus", "2", "--launch-selftest"], {"MSWEEP_SELFTEST_FAIL_RANK": "1"})
     assert r.returncode != 0 and "ranks failed" in r.stderr and "rank 1" in r.stderr
     assert time.time() - t0 < 120
+
+
+def test_bench_dump_outputs_writes_float64_and_samples_beyond_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; past the cap in all, the same seeded sample of each
+    array's flattened elements, in order, so that two builds still compare element for element."""
+    import importlib.util
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    theta = np.random.default_rng(3).random((40, 50))
+    bench.dump_outputs(str(tmp_path / "small"), {"theta": theta.astype(np.float32), "bound": [-1.5]})
+    got = np.load(tmp_path / "small" / "theta.npy")
+    assert got.dtype == np.float64 and got.shape == (40, 50)
+    np.testing.assert_array_equal(got, theta.astype(np.float32))
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "bound.npy"), [-1.5])
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 8 * 500)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"theta": theta, "iters": np.arange(1000)})
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("theta", "iters")}
+    assert sum(v.nbytes for v in a.values()) <= 8 * 500
+    assert a["theta"].size == 2000 * 500 // 3000 and a["iters"].size == 1000 * 500 // 3000
+    assert np.all(np.diff(a["iters"]) > 0) and np.isin(a["theta"], theta).all()
+    for n in a:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / (n + ".npy")), a[n])

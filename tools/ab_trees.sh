@@ -7,7 +7,7 @@
 # (profiles/r04_vs_r03_same_box.txt).  Remove the worktree afterwards: git worktree remove --force build_ab/old_tree
 old=$1
 shift
-run() { (cd $2 && python bench.py $1 --no-cpu-baseline --no-extras 2> /tmp/ab_err.log | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', '$2', round(d['ms_per_step'],4), {k: round(v,4) for k,v in d['kernels'].items() if k.endswith('ms')})" || tail -5 /tmp/ab_err.log); }
+run() { (cd $2 && python bench.py $1 $(grep -q -- '"--full"' bench.py && echo --full) --no-cpu-baseline --no-extras 2> /tmp/ab_err.log | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', '$2', round(d['ms_per_step'],4), {k: round(v,4) for k,v in d['kernels'].items() if k.endswith('ms')})" || tail -5 /tmp/ab_err.log); }
 for args in "$@"; do
   for tree in . $old . $old; do run "$args" $tree; done
 done
