@@ -187,6 +187,29 @@ int msw_core_gamma(msw_handle h, double *gamma_out, size_t ld);
  * is hundreds of GB (G x E x 8 B = 375 GB at 10 M reads x 5 k groups), a block of it is not. */
 int msw_core_gamma_block(msw_handle h, size_t ec_begin, size_t ec_end, double *gamma_out, size_t ld);
 
+/* mGEMS read binning (src/mSWEEP.cpp:437-469, mGEMS::BinFromMatrix) on the device, from the last solve: the reads of
+ * EC j go to the bin of target k when gamma(targets[k], j) >= log(thresholds[k]) -- the gamma msw_core_gamma_block
+ * returns, bit for bit, and log(t_k) formed on the host.  Within a bin: ECs in EC order, the reads of an EC as
+ * ec_reads holds them (Alignment::get_aligned_reads, include/mSWEEP_alignment.hpp:224).
+ *   ec_rptr[n_ecs + 1] / ec_reads[ec_rptr[n_ecs]]  the read ids of every EC (msw_alignment_export); n_ecs = the handle's E
+ *   targets[n_targets]     rows of the kept groups (0 .. n_groups_out - 1), each at most once
+ *   thresholds[n_targets]  probabilities t_k in [0, 1] (the drivers pass 1 - theta_k)
+ *   bin_ptr[n_targets + 1] always written: bin k = reads_out[bin_ptr[k] .. bin_ptr[k + 1])
+ *   reads_out              NULL: sizes only; else bin_ptr[n_targets] read ids
+ *   log_thr_out            optional: the log(t_k) the comparison used
+ * Device memory O(E + pairs + output), never G x E; an output that cannot be allocated is an error naming the bytes.
+ * Refused (non-zero, msw_last_error): no solve yet, n_ecs != E, a target out of range or repeated, a threshold NaN or
+ * outside [0, 1], the dense flavour (set_dense_logl with MSWEEP_DENSE_COMPRESS=0), a communicator set.  Every call runs
+ * the whole pass (nothing is cached between a sizes call and a fill call). */
+int msw_core_bin_reads(msw_handle h, const uint64_t *ec_rptr, const uint32_t *ec_reads, size_t n_ecs,
+                       const uint32_t *targets, const double *thresholds, size_t n_targets, uint64_t *bin_ptr,
+                       uint32_t *reads_out, double *log_thr_out);
+/* The same on an alignment handle: classes resident on h's device (msw_alignment_read_device) are read where they lie,
+ * any other handle's host arrays are uploaded. */
+struct msw_alignment;
+int msw_core_bin_reads_aln(msw_handle h, struct msw_alignment *a, const uint32_t *targets, const double *thresholds,
+                           size_t n_targets, uint64_t *bin_ptr, uint32_t *reads_out, double *log_thr_out);
+
 /* Per-iteration diagnostics of the last solve (what rcgpar logs every 5th iteration to
  * the verbose stream, src/mSWEEP.cpp:198): arrays of length n (<= max recorded, 4096);
  * theta_trace is n x G or NULL.  Returns the number of iterations recorded via *n_out. */

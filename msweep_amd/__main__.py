@@ -1,12 +1,13 @@
 """`python -m msweep_amd` -- the estimation part of mSWEEP's command line (src/mSWEEP.cpp:68-148)
-over the MI355X core: Themisto plaintext in, `<prefix>_abundances.txt` out.  Only the flags that
-reach the hot path are accepted; binning, likelihood dumps and compression are out of scope."""
+over the MI355X core: Themisto plaintext in, `<prefix>_abundances.txt` out, and with --bin-reads the
+mGEMS bins `<dir>/<group>.bin` (src/mSWEEP.cpp:437-469; the bin pass runs on the device, msweep_amd/binning.py
+holds the driver's side).  Compression of the outputs is out of scope."""
 import argparse
 import sys
 
 import numpy as np
 
-from . import parallel
+from . import binning, parallel
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, Core, MswError
 from .likelihood import from_device_alignment, from_dense
 from .reference import read_reference
@@ -40,6 +41,9 @@ def parse(argv):
     ap.add_argument("--write-likelihood", action="store_true")
     ap.add_argument("--read-likelihood")
     ap.add_argument("--no-fit-model", action="store_true")
+    ap.add_argument("--bin-reads", action="store_true")
+    ap.add_argument("--target-groups", type=lambda v: v.split(","))
+    ap.add_argument("--min-abundance", type=float)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
@@ -99,9 +103,35 @@ def dirichlet_kld_rate(alphas):
     return np.exp(log_kld), np.exp(log_kld - lsum)
 
 
+def bin_reads(core, aln, estimated_names, theta, a):
+    """--bin-reads (src/mSWEEP.cpp:437-469): targets, thresholds 1 - theta, the bins from the device, one file per
+    target (an empty bin gives an empty file).  Returns the exit status."""
+    try:
+        targets = binning.resolve_targets(estimated_names, a.target_groups)
+        if a.min_abundance is not None:
+            targets = binning.filter_min_abundance(targets, estimated_names, theta, a.min_abundance)
+        row = {n: i for i, n in enumerate(estimated_names)}
+        rows = [row[t] for t in targets]
+        bin_ptr, reads, _ = core.bin_reads_aln(aln, rows, binning.thresholds(rows, theta))
+    except (binning.BinningError, MswError) as ex:
+        sys.stderr.write(f"Binning the reads failed:\n  {ex}\nexiting\n")
+        return 1
+    for k, name in enumerate(targets):
+        try:
+            binning.write_bin(binning.bin_path(a.prefix, name), reads[int(bin_ptr[k]):int(bin_ptr[k + 1])])
+        except OSError as ex:
+            sys.stderr.write(f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
+            return 1
+    return 0
+
+
 def main(argv=None):
     a = parse(sys.argv[1:] if argv is None else argv)
     aln = None
+    if a.bin_reads and a.read_likelihood:
+        # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
+        sys.stderr.write("Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n")
+        return 1
     try:
         core = Core(a.device)
     except MswError as ex:
@@ -172,14 +202,24 @@ def main(argv=None):
             for k in range(0, t["n"], 5):
                 sys.stderr.write(f"  iter: {k}, bound: {t['bound'][k]:g}, |g|: {t['newnorm'][k]:g}\n")
         sample.store_abundances(res["theta"])
+    except MswError as ex:
+        sys.stderr.write(f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
+        return 1
+    if a.bin_reads:
+        # before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
+        est = [n for n, m in zip(grouping.get_names(), lik.groups_considered()) if m]
+        rc = bin_reads(core, aln, est, res["theta"], a)
+        if rc:
+            return rc
+    try:
         if a.iters > 0:
             if a.seed == 26012023:      # the reference's "random seed" sentinel (src/BootstrapSample.cpp:48-50)
                 seed = int(np.random.SeedSequence().generate_state(1)[0] & 0x7fffffff)
             else:
                 seed = ((a.seed + 2**31) % 2**32) - 2**31            # size_t -> int32 narrowing (Sample.hpp:169)
-            # ConstructSample quirk (src/Sample.cpp:38-39): --bootstrap-count without --bin-reads
-            # passes the number of ITERATIONS as the count
-            draws = a.iters if a.bootstrap_count > 0 else total
+            # ConstructSample (src/Sample.cpp:30-50): --bootstrap-count is the number of draws with --bin-reads;
+            # the quirk without it passes the number of ITERATIONS as the count
+            draws = (a.bootstrap_count if a.bin_reads else a.iters) if a.bootstrap_count > 0 else total
             w = ec_counts.astype(np.uint32)
             thetas, _ = core.bootstrap(w, seed, draws, 0, a.iters, prior, a.tol, a.max_iters, algo, prec)
             for row in thetas:

@@ -33,7 +33,7 @@ EXPORTS = [
     "msw_comm_destroy", "msw_core_set_comm", "msw_comm_last_error", "msw_core_bootstrap_dist",
     "msw_comm_size", "msw_comm_rccl_count", "msw_comm_allgather", "msw_comm_allreduce", "msw_comm_create_shm", "msw_core_continue", "msw_core_gamma_block",
     "msw_core_last_bootstrap_timing", "msw_core_layout_info", "msw_core_guarded_visits", "msw_core_set_pack_schedule",
-    "msw_core_set_option", "msw_core_get_option",
+    "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
 ]
 
 
@@ -123,6 +123,8 @@ def load_library():
     L.msw_core_continue.argtypes = [vp, sz, vp, C.POINTER(sz), C.POINTER(dp)]
     L.msw_core_gamma.argtypes = [vp, vp, sz]
     L.msw_core_gamma_block.argtypes = [vp, sz, sz, vp, sz]
+    L.msw_core_bin_reads.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+    L.msw_core_bin_reads_aln.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
     L.msw_core_trace.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.msw_core_set_trace_theta.argtypes = [vp, sz]
     L.msw_core_bootstrap.argtypes = [vp, vp, C.c_int32, sz, sz, sz, vp, dp, sz, C.c_int, C.c_int, vp, vp]
@@ -453,6 +455,38 @@ class Core:
         out = np.empty((G, max(w, 0)))
         self._check(self._L.msw_core_gamma_block(self._h, int(ec_begin), int(ec_end), _ptr(out), max(w, 1)))
         return out
+
+    def bin_reads(self, ec_rptr, ec_reads, targets, thresholds, want_reads=True):
+        """mGEMS read binning of the last solve on the device (msw_core_bin_reads): the reads of EC j go to bin k when
+        gamma(targets[k], j) >= log(thresholds[k]).  Returns (bin_ptr[n_targets + 1] uint64, reads uint32 or None,
+        log_thr[n_targets]); bin k = reads[bin_ptr[k]:bin_ptr[k + 1]]."""
+        ec_rptr = _arr(ec_rptr, np.uint64)
+        ec_reads = _arr(ec_reads, np.uint32)
+        if len(ec_rptr) == 0 or (len(ec_rptr) and int(ec_rptr[-1]) > len(ec_reads)):
+            raise MswError("bin_reads: ec_rptr does not describe ec_reads")
+        return self._bin(lambda t, th, n, bp, out, lt: self._L.msw_core_bin_reads(
+            self._h, _ptr(ec_rptr), _ptr(ec_reads), len(ec_rptr) - 1, t, th, n, bp, out, lt), targets, thresholds, want_reads)
+
+    def bin_reads_aln(self, aln, targets, thresholds, want_reads=True):
+        """bin_reads on the classes of an alignment (msw_core_bin_reads_aln): a DeviceAlignment on this GPU is read
+        where it lies."""
+        return self._bin(lambda t, th, n, bp, out, lt: self._L.msw_core_bin_reads_aln(
+            self._h, aln._h, t, th, n, bp, out, lt), targets, thresholds, want_reads)
+
+    def _bin(self, call, targets, thresholds, want_reads):
+        targets = _arr(targets, np.uint32)
+        thresholds = _arr(thresholds, np.float64)
+        if targets.shape != thresholds.shape or targets.ndim != 1:
+            raise MswError("bin_reads: targets and thresholds must be 1-D arrays of one length")
+        n = len(targets)
+        bin_ptr = np.zeros(n + 1, np.uint64)
+        log_thr = np.empty(n, np.float64)
+        self._check(call(_ptr(targets), _ptr(thresholds), n, _ptr(bin_ptr), None, _ptr(log_thr)))
+        if not want_reads:
+            return bin_ptr, None, log_thr
+        reads = np.empty(int(bin_ptr[-1]), np.uint32)
+        self._check(call(_ptr(targets), _ptr(thresholds), n, _ptr(bin_ptr), _ptr(reads), None))
+        return bin_ptr, reads, log_thr
 
     def set_trace_theta(self, n):
         self._check(self._L.msw_core_set_trace_theta(self._h, int(n)))

@@ -6,12 +6,15 @@
 // PlainSample / BootstrapSample::write_abundances[2] (src/PlainSample.cpp:32-71,
 // src/BootstrapSample.cpp:75-130), plus the consumers around the path: --write-probs / --print-probs (Sample::write_probs,
 // src/Sample.cpp:63-85,154-186: streamed from the device in blocks of ECs), --write-likelihood / --read-likelihood /
-// --no-fit-model (include/Likelihood.hpp:224-273, src/mSWEEP.cpp:357-386) and --run-rate (src/Sample.cpp:99-152,
-// src/mSWEEP.cpp:524-548).  Same flags and messages as the reference for what it covers; held byte-for-byte against
+// --no-fit-model (include/Likelihood.hpp:224-273, src/mSWEEP.cpp:357-386), --run-rate (src/Sample.cpp:99-152,
+// src/mSWEEP.cpp:524-548) and --bin-reads / --target-groups / --min-abundance (the mGEMS bins, src/mSWEEP.cpp:437-469:
+// the bin pass on the device, msw_core_bin_reads_aln; the driver's choices are those of msweep_amd/binning.py).  Same flags and messages as the reference for what it covers; held byte-for-byte against
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
 //
 //   g++ -std=c++17 -O2 -o msweep_mini msweep_mini.cpp -L.. -lmsweep_core -Wl,-rpath,..
 #include <algorithm>
+#include <cerrno>
+#include <charconv>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +26,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -41,6 +45,9 @@ struct Args {
   bool verbose = false;
   bool write_probs = false, print_probs = false, write_likelihood = false, no_fit_model = false, run_rate = false;
   std::string read_likelihood;
+  bool bin_reads = false, have_target_groups = false, have_min_abundance = false;
+  std::vector<std::string> target_groups;
+  double min_abundance = 0.0;
 };
 
 std::vector<std::string> split(const std::string &s, char d) {
@@ -87,6 +94,14 @@ Args parse(int argc, char **argv) {
     else if (k == "--read-likelihood") a.read_likelihood = val();
     else if (k == "--no-fit-model") a.no_fit_model = true;
     else if (k == "--run-rate") a.run_rate = true;
+    else if (k == "--bin-reads") a.bin_reads = true;
+    else if (k == "--target-groups") {
+      a.target_groups = split(val(), ',');
+      a.have_target_groups = true;
+    } else if (k == "--min-abundance") {
+      a.min_abundance = std::stod(val());
+      a.have_min_abundance = true;
+    }
     else throw std::runtime_error("unknown argument " + k);
   }
   if (a.themisto.empty()) {
@@ -157,6 +172,113 @@ void read_likelihood_file(const std::string &path, size_t G, std::vector<uint64_
     for (size_t g = 0; g < G; ++g) L[g * E + j] = cols[j][g];
 }
 
+// ---- --bin-reads (src/mSWEEP.cpp:437-469; the same choices as msweep_amd/binning.py) ---------------------------------
+struct BinningError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+
+// targets: every estimated group in group order, or --target-groups in the order given (a repeated name once); a
+// name that is not an estimated group (unknown, or pruned by --min-hits) is refused.  --min-abundance m drops a
+// target with theta < m (mGEMS::FilterTargetGroups), ties kept.  Returns the rows of the kept groups.
+std::vector<uint32_t> bin_targets(const Args &a, const std::vector<std::string> &est, const std::vector<double> &theta,
+                                  std::vector<std::string> &names) {
+  std::unordered_map<std::string, uint32_t> row;
+  for (size_t i = 0; i < est.size(); ++i) row.emplace(est[i], (uint32_t)i);
+  names.clear();
+  for (const std::string &n : a.have_target_groups ? a.target_groups : est) {
+    if (!row.count(n)) throw BinningError("target group " + n + " is not among the estimated groups");
+    if (std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n);
+  }
+  std::vector<uint32_t> rows;
+  std::vector<std::string> kept;
+  for (const std::string &n : names) {
+    const uint32_t r = row[n];
+    if (a.have_min_abundance && theta[r] < a.min_abundance) continue;
+    rows.push_back(r);
+    kept.push_back(n);
+  }
+  names = std::move(kept);
+  return rows;
+}
+
+// OutfileDesignator::bin (src/OutfileDesignator.cpp:80-93): `-o` up to its last '/', or '.', then /<name>.bin
+std::string bin_path(const std::string &prefix, const std::string &name) {
+  const size_t s = prefix.rfind('/');
+  return (s == std::string::npos ? std::string(".") : prefix.substr(0, s)) + "/" + name + ".bin";
+}
+
+// min(16, hardware threads, the cgroup's CPU quota): the reader's rule (msweep_amd/csrc/host_alignment.inc)
+size_t writer_threads() {
+  size_t n = std::max<size_t>(1, std::min<size_t>(16, std::thread::hardware_concurrency()));
+  if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
+    char q[64] = {0};
+    unsigned long long period = 0;
+    if (fscanf(f, "%63s %llu", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0)
+      n = std::max<size_t>(1, std::min<size_t>(n, (size_t)(strtoull(q, nullptr, 10) / period)));
+    fclose(f);
+  }
+  return n;
+}
+
+// mGEMS::WriteBin: one decimal id per line, each line ending in '\n'; formatted with std::to_chars into 8 MB buffers.
+// Returns an error text, empty on success.
+std::string write_bin(const std::string &path, const uint32_t *ids, size_t n) {
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f) return "cannot open " + path + ": " + strerror(errno);
+  constexpr size_t kBuf = 8u << 20;
+  std::vector<char> buf(kBuf);
+  size_t used = 0;
+  std::string err;
+  for (size_t i = 0; i < n && err.empty(); ++i) {
+    if (kBuf - used < 16) {
+      if (fwrite(buf.data(), 1, used, f) != used) err = "cannot write " + path + ": " + strerror(errno);
+      used = 0;
+    }
+    char *e = std::to_chars(buf.data() + used, buf.data() + kBuf, ids[i]).ptr;
+    *e++ = '\n';
+    used = (size_t)(e - buf.data());
+  }
+  if (err.empty() && used && fwrite(buf.data(), 1, used, f) != used) err = "cannot write " + path + ": " + strerror(errno);
+  if (fclose(f) != 0 && err.empty()) err = "cannot close " + path + ": " + strerror(errno);
+  return err;
+}
+
+// the bins from the device and one file per target (an empty bin: an empty file), written on up to writer_threads()
+// threads; returns the exit status
+int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vector<std::string> &est,
+              const std::vector<double> &theta) {
+  std::vector<std::string> names;
+  std::vector<uint64_t> bin_ptr;
+  std::vector<uint32_t> reads;
+  try {
+    const std::vector<uint32_t> rows = bin_targets(a, est, theta, names);
+    std::vector<double> thr(rows.size());
+    for (size_t k = 0; k < rows.size(); ++k) thr[k] = 1.0 - theta[rows[k]];
+    bin_ptr.assign(rows.size() + 1, 0);
+    check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), nullptr, nullptr));
+    reads.resize(bin_ptr.back());
+    check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), reads.data(), nullptr));
+  } catch (const std::exception &ex) {
+    std::cerr << "Binning the reads failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  const size_t n = names.size(), nt = std::min(n, writer_threads());
+  std::vector<std::string> err(n);
+  std::vector<std::thread> pool;
+  for (size_t t = 0; t < nt; ++t)
+    pool.emplace_back([&, t] {
+      for (size_t k = t; k < n; k += nt)
+        err[k] = write_bin(bin_path(a.prefix, names[k]), reads.data() + bin_ptr[k], bin_ptr[k + 1] - bin_ptr[k]);
+    });
+  for (auto &th : pool) th.join();
+  for (size_t k = 0; k < n; ++k)
+    if (!err[k].empty()) {
+      std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
+      return 1;
+    }
+  return 0;
+}
+
 // Sample::write_probs[2] (src/Sample.cpp:63-85,154-186): header `ec_id` + group names, one line per equivalence class
 // of exp(gamma); the G x E matrix is streamed from the device 8192 classes at a time (msw_core_gamma_block)
 void write_probs(std::ostream &of, msw_handle h, const std::vector<std::string> &names, const std::vector<std::string> &zero_names,
@@ -224,6 +346,11 @@ int main(int argc, char **argv) {
     a = parse(argc, argv);
   } catch (const std::exception &ex) {
     std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  if (a.bin_reads && !a.read_likelihood.empty()) {
+    // "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
+    std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
     return 1;
   }
   Grouping grouping;
@@ -345,6 +472,14 @@ int main(int argc, char **argv) {
       }
     }
     results.push_back(theta);
+    if (a.bin_reads) {
+      // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
+      if (bin_reads(a, h, aln_keep, est_names, theta) != 0) {
+        msw_alignment_destroy(aln_keep);
+        msw_core_destroy(h);
+        return 1;
+      }
+    }
     if (a.iters > 0) {
       int32_t seed;
       if (a.seed == 26012023) {  // the reference's "random seed" sentinel (src/BootstrapSample.cpp:48-50)
@@ -352,9 +487,9 @@ int main(int argc, char **argv) {
       } else {
         seed = (int32_t)(uint32_t)a.seed;  // size_t -> int32 narrowing (include/Sample.hpp:169)
       }
-      // ConstructSample quirk (src/Sample.cpp:38-39): --bootstrap-count without --bin-reads passes the
-      // number of ITERATIONS as the count
-      const size_t draws = a.bootstrap_count > 0 ? a.iters : (size_t)total;
+      // ConstructSample (src/Sample.cpp:30-50): --bootstrap-count is the number of draws with --bin-reads; the quirk
+      // without it passes the number of ITERATIONS as the count
+      const size_t draws = a.bootstrap_count > 0 ? (a.bin_reads ? a.bootstrap_count : a.iters) : (size_t)total;
       std::vector<uint32_t> w(ec_counts.begin(), ec_counts.end());
       std::vector<double> thetas(a.iters * n_kept);
       check(h, msw_core_bootstrap(h, w.data(), seed, draws, 0, a.iters, prior.data(), a.tol, a.max_iters, algo, prec,

@@ -16,10 +16,45 @@ __global__ __launch_bounds__(256) void k_invert_perm(const uint32_t *perm, uint3
   if (p < E) iperm[perm[p]] = p;
 }
 
+// The per-EC normaliser of gamma and the value of one cell, shared by k_gamma_block and the bin pass
+// (bin_kernels.hpp): both compute gamma(g, j) with these very expressions, so a read binned on the device is binned
+// by the same bits msw_core_gamma_block returns.  gamma_norm_consts: M = max_g u_g and U = sum_g exp(u_g - M) over
+// the block (256 threads: the order of block_sum's additions depends on the block size); p0 = exp(a (logzi - tref)).
+__device__ __forceinline__ void gamma_norm_consts(uint32_t G, const double *u, double *sh, double &M, double &U) {
+  const int tid = threadIdx.x;
+  double m = -INFINITY;
+  for (uint32_t g = tid; g < G; g += blockDim.x) m = fmax(m, u[g]);
+  M = block_max(m, sh);
+  double su = 0.0;
+  for (uint32_t g = tid; g < G; g += blockDim.x) su += exp(u[g] - M);
+  U = block_sum(su, sh);
+}
+// lse_j of the EC at permuted position p: every exp(a T) relative to tref (the table value with the largest a T, log zi
+// included): <= 1
+template <int ENC>
+__device__ __forceinline__ double gamma_lse(const SellDev &S, uint32_t p, double a, double tref, const double *u,
+                                            double M, double U, double p0) {
+  double zs = 0.0;
+  for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { zs += exp(u[g] - M) * (exp(a * (T - tref)) - p0); });
+  double Z = p0 * U + zs;
+  if (!(Z >= p0 * U * kGuardRatio)) {  // guarded EC (sell.hpp): every group visited instead
+    Z = 0.0;
+    for (uint32_t g = 0; g < S.n_groups; ++g) {
+      double xg = p0;
+      for_each_cell<ENC>(S, p, [&](uint32_t gg, double T) { if (gg == g) xg = exp(a * (T - tref)); });
+      Z += exp(u[g] - M) * xg;
+    }
+  }
+  return M + log(Z) + a * tref;
+}
+// gamma of one cell: T = the listed value, or log zi for the background
+__device__ __forceinline__ double gamma_cell(double a, double T, double ug, double lse) { return a * T + ug - lse; }
+
 // gamma (or, with (a, u, lse) = (1, 0, none), the likelihood itself) of the ECs [e0, e1) in the ORIGINAL EC
 // order: out[g * ld + (j - e0)], all groups.  A thread per EC: its normaliser lse_j, the background value
-// of every group, then its listed cells.  What msw_core_gamma_block serves --write-probs / the binning input
-// from, block by block (src/Sample.cpp:63-85, src/mSWEEP.cpp:437-469), without a G x E buffer anywhere.
+// of every group, then its listed cells.  What msw_core_gamma_block serves --write-probs from, block by block
+// (src/Sample.cpp:63-85), without a G x E buffer anywhere; the binning of src/mSWEEP.cpp:437-469 runs on the same
+// expressions in bin_kernels.hpp.
 template <int ENC>
 __global__ __launch_bounds__(256) void k_gamma_block(SellDev S, const uint32_t *iperm, uint32_t e0, uint32_t e1,
                                                     double a, double logzi, double tref, const double *u,
@@ -27,36 +62,14 @@ __global__ __launch_bounds__(256) void k_gamma_block(SellDev S, const uint32_t *
   __shared__ double sh[32];
   const int tid = threadIdx.x;
   double M = 0.0, U = 0.0;
-  if (normalise) {
-    double m = -INFINITY;
-    for (uint32_t g = tid; g < S.n_groups; g += blockDim.x) m = fmax(m, u[g]);
-    M = block_max(m, sh);
-    double su = 0.0;
-    for (uint32_t g = tid; g < S.n_groups; g += blockDim.x) su += exp(u[g] - M);
-    U = block_sum(su, sh);
-  }
-  // every exp(a T) relative to tref (the table value with the largest a T, log zi included): <= 1
+  if (normalise) gamma_norm_consts(S.n_groups, u, sh, M, U);
   const double p0 = exp(a * (logzi - tref));
   for (uint32_t j = e0 + blockIdx.x * blockDim.x + tid; j < e1; j += gridDim.x * blockDim.x) {
     const uint32_t p = iperm[j];
-    double lse = 0.0;
-    if (normalise) {
-      double zs = 0.0;
-      for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { zs += exp(u[g] - M) * (exp(a * (T - tref)) - p0); });
-      double Z = p0 * U + zs;
-      if (!(Z >= p0 * U * kGuardRatio)) {  // guarded EC (sell.hpp): every group visited instead
-        Z = 0.0;
-        for (uint32_t g = 0; g < S.n_groups; ++g) {
-          double xg = p0;
-          for_each_cell<ENC>(S, p, [&](uint32_t gg, double T) { if (gg == g) xg = exp(a * (T - tref)); });
-          Z += exp(u[g] - M) * xg;
-        }
-      }
-      lse = M + log(Z) + a * tref;
-    }
+    const double lse = normalise ? gamma_lse<ENC>(S, p, a, tref, u, M, U, p0) : 0.0;
     double *col = out + (j - e0);
-    for (uint32_t g = 0; g < S.n_groups; ++g) col[(size_t)g * ld] = a * logzi + u[g] - lse;
-    for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { col[(size_t)g * ld] = a * T + u[g] - lse; });
+    for (uint32_t g = 0; g < S.n_groups; ++g) col[(size_t)g * ld] = gamma_cell(a, logzi, u[g], lse);
+    for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { col[(size_t)g * ld] = gamma_cell(a, T, u[g], lse); });
   }
 }
 

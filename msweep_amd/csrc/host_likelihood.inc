@@ -558,6 +558,18 @@ void set_dense_impl(msw_core *h, const double *L, size_t G, size_t E, size_t ld)
 
 // gamma (or the likelihood itself) of the ECs [e0, e1), rows = groups, columns in the caller's EC order:
 // out[g * ld + (j - e0)].  Computed in column blocks of at most 2^27 / G ECs on the device.
+// (a, tref, u) of gamma after the last solve: RCG's scaled state, or EM's u = log(theta) of the last M-step with a = 1;
+// tref = the table value with the largest a T.  What k_gamma_block and the bin pass (host_bin.inc) both read.
+struct GammaState {
+  double a, tref;
+  const double *u;
+};
+GammaState gamma_state(msw_core *h) {
+  poll(h);
+  const double a = h->last_algo == MSW_ALGO_EM ? 1.0 : h->sc_host->a;
+  return GammaState{a, a >= 0.0 ? h->sc_host->tmax : h->sc_host->tmin, h->u.p};
+}
+
 void materialise_impl(msw_core *h, double *out, size_t ld, bool gamma, size_t e0, size_t e1) {
   if (h->flavor < 0) throw Fail("no likelihood resident");
   if (!out) throw Fail("null output");
@@ -569,10 +581,10 @@ void materialise_impl(msw_core *h, double *out, size_t ld, bool gamma, size_t e0
   DevBuf<double> zero_u;
   const double *u = nullptr;
   if (gamma) {
-    poll(h);
-    a = h->last_algo == MSW_ALGO_EM ? 1.0 : h->sc_host->a;  // EM: u = log(theta) of the last M-step
-    tref = a >= 0.0 ? h->sc_host->tmax : h->sc_host->tmin;
-    u = h->u.p;
+    const GammaState gs = gamma_state(h);
+    a = gs.a;
+    tref = gs.tref;
+    u = gs.u;
   } else {
     zero_u.alloc(G);
     zero_u.zero(h->stream);

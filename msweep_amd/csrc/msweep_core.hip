@@ -20,6 +20,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "kernels.hpp"
@@ -34,6 +35,7 @@
 #include "em_f32_kernels.hpp"
 #include "stream_kernels.hpp"
 #include "reader_kernels.hpp"
+#include "bin_kernels.hpp"
 
 using namespace msw;
 
@@ -936,6 +938,7 @@ struct StageTimer {
 #include "host_compress.inc"
 #include "host_alignment.inc"
 #include "host_reader.inc"
+#include "host_bin.inc"
 
 // =========================================================================================
 // C ABI
@@ -1148,6 +1151,30 @@ int msw_core_gamma_block(msw_handle h, size_t ec_begin, size_t ec_end, double *g
   return guarded(h, [&] {
     if (!h->have_solution) throw Fail("msw_core_gamma_block: no solve has run on this handle");
     materialise_impl(h, gamma_out, ld, /*gamma=*/true, ec_begin, ec_end);
+  });
+}
+
+int msw_core_bin_reads(msw_handle h, const uint64_t *ec_rptr, const uint32_t *ec_reads, size_t n_ecs,
+                       const uint32_t *targets, const double *thresholds, size_t n_targets, uint64_t *bin_ptr,
+                       uint32_t *reads_out, double *log_thr_out) {
+  return guarded(h, [&] {
+    bin_reads_impl(h, ec_rptr, ec_reads, n_ecs, false, targets, thresholds, n_targets, bin_ptr, reads_out, log_thr_out);
+  });
+}
+
+int msw_core_bin_reads_aln(msw_handle h, msw_alignment_t a, const uint32_t *targets, const double *thresholds,
+                           size_t n_targets, uint64_t *bin_ptr, uint32_t *reads_out, double *log_thr_out) {
+  return guarded(h, [&] {
+    if (!a) throw Fail("msw_core_bin_reads_aln: null alignment");
+    if (a->on_device && a->device == h->device) {
+      // the reader's classes are read where they lie
+      bin_reads_impl(h, a->d_rptr.p, a->d_reads.p, a->E, true, targets, thresholds, n_targets, bin_ptr, reads_out,
+                     log_thr_out);
+    } else {
+      a->to_host(msw_alignment::kAlnRptr | msw_alignment::kAlnReads);
+      bin_reads_impl(h, a->ec_rptr.data(), a->ec_reads.data(), a->ec_rptr.empty() ? 0 : a->ec_rptr.size() - 1, false,
+                     targets, thresholds, n_targets, bin_ptr, reads_out, log_thr_out);
+    }
   });
 }
 
