@@ -22,22 +22,24 @@ void bin_alloc(DevBuf<T> &b, size_t count, const char *what) {
 template <int ENC, bool LDS>
 void launch_bin_passes(msw_core *h, const GammaState &gs, const BinTargets &B, double *lse_p, uint32_t *cnt,
                        const uint64_t *off, uint32_t *key, uint32_t *val, bool write) {
-  const size_t lds = LDS ? (size_t)h->G * sizeof(uint32_t) : 0;
-  const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)h->E + 255) / 256, (size_t)h->n_cu * 8));
+  const Resident &L = h->lik;
+  const size_t lds = LDS ? (size_t)L.G * sizeof(uint32_t) : 0;
+  const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)L.E + 255) / 256, (size_t)h->n_cu * 8));
   if (!write)
-    hipLaunchKernelGGL((k_bin_count<ENC, LDS>), dim3(nb), dim3(256), lds, h->stream, sell_view(h), gs.a, h->logzi,
+    hipLaunchKernelGGL((k_bin_count<ENC, LDS>), dim3(nb), dim3(256), lds, h->stream, sell_view(L, h->solver), gs.a, L.logzi,
                        gs.tref, gs.u, B, lse_p, cnt);
   else
-    hipLaunchKernelGGL((k_bin_write<ENC, LDS>), dim3(nb), dim3(256), lds, h->stream, sell_view(h), gs.a, h->logzi, gs.u,
+    hipLaunchKernelGGL((k_bin_write<ENC, LDS>), dim3(nb), dim3(256), lds, h->stream, sell_view(L, h->solver), gs.a, L.logzi, gs.u,
                        B, lse_p, off, key, val);
   MSW_HIP(hipGetLastError());
 }
 template <bool LDS>
 void launch_bin_enc(msw_core *h, const GammaState &gs, const BinTargets &B, double *lse_p, uint32_t *cnt,
                     const uint64_t *off, uint32_t *key, uint32_t *val, bool write) {
-  if (h->enc == kEncValue) launch_bin_passes<kEncValue, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
-  else if (h->wide()) launch_bin_passes<kEncWide, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
-  else if (h->hybrid()) launch_bin_passes<kEncIndex, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
+  const Resident &L = h->lik;
+  if (L.enc == kEncValue) launch_bin_passes<kEncValue, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
+  else if (L.wide()) launch_bin_passes<kEncWide, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
+  else if (L.hybrid()) launch_bin_passes<kEncIndex, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
   else launch_bin_passes<kEncNarrow, LDS>(h, gs, B, lse_p, cnt, off, key, val, write);
 }
 
@@ -50,17 +52,18 @@ bool bin_slots_in_lds(uint32_t G) {
 void bin_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads, size_t n_ecs, bool on_device,
                     const uint32_t *targets, const double *thresholds, size_t n_targets, uint64_t *bin_ptr,
                     uint32_t *reads_out, double *log_thr_out) {
-  if (!h->have_solution) throw Fail("msw_core_bin_reads: no solve has run on this handle");
+  const Resident &L = h->lik;
+  if (!h->solver.have_solution) throw Fail("msw_core_bin_reads: no solve has run on this handle");
   if (h->comm) throw Fail("msw_core_bin_reads: not available on an EC-sharded handle (a communicator is set)");
-  if (h->flavor != 0)
+  if (L.flavor != 0)
     throw Fail("msw_core_bin_reads: the resident likelihood has the dense flavour; binning needs the CSR-of-ECs layout");
-  if (n_ecs != h->E)
+  if (n_ecs != L.E)
     throw Fail("msw_core_bin_reads: " + std::to_string(n_ecs) + " equivalence classes given, the handle holds " +
-               std::to_string(h->E));
+               std::to_string(L.E));
   if (!bin_ptr) throw Fail("msw_core_bin_reads: null bin_ptr");
   if (n_targets && (!targets || !thresholds)) throw Fail("msw_core_bin_reads: null targets or thresholds");
   if (n_targets >= (size_t)kNoSlot) throw Fail("msw_core_bin_reads: too many targets");
-  const uint32_t G = h->G, E = h->E;
+  const uint32_t G = L.G, E = L.E;
   std::vector<uint32_t> slot_of(G, kNoSlot);
   std::vector<double> logt(n_targets);
   for (size_t k = 0; k < n_targets; ++k) {
@@ -99,13 +102,13 @@ void bin_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads, si
   }
 
   // targets, thresholds and the background prefilter (bin_kernels.hpp: BinTargets)
-  const GammaState gs = gamma_state(h);
+  const GammaState gs = gamma_state(h->solver);
   std::vector<double> u(G);
   MSW_HIP(hipMemcpyAsync(u.data(), gs.u, G * sizeof(double), hipMemcpyDeviceToHost, st));
   MSW_HIP(hipStreamSynchronize(st));
   double cmax = -INFINITY, mag = 0.0;
   for (size_t k = 0; k < n_targets; ++k) {
-    const double x = gs.a * h->logzi, ug = u[targets[k]];
+    const double x = gs.a * L.logzi, ug = u[targets[k]];
     const double c = x + ug - logt[k];
     cmax = std::isnan(c) ? INFINITY : std::max(cmax, c);
     for (double v : {x, ug, logt[k]})

@@ -58,56 +58,56 @@ constexpr uint64_t kMtJumpMin = 1ull << 27;  // words from which the host jump b
 
 // Positions the device Mersenne-Twister stream at word `target` (re-seeding when it has to
 // move backwards or the seed changed).
-void mt_seek(msw_core *h, int32_t seed, uint64_t target, hipStream_t st) {
-  h->mt.alloc(1);
-  bool reseed = !h->mt_valid || h->mt_seed != seed || h->mt_pos > target;
+void mt_seek(Resampler &r, int32_t seed, uint64_t target, hipStream_t st) {
+  r.mt.alloc(1);
+  bool reseed = !r.mt_valid || r.mt_seed != seed || r.mt_pos > target;
   if (reseed) {
     // std::mt19937_64(int32 seed): the seed converts to uint64 (sign-extends)
-    hipLaunchKernelGGL(k_mt64_seed, dim3(1), dim3(64), 0, st, h->mt.p, (uint64_t)(int64_t)seed);
-    h->mt_pos = 0;
-    h->mt_seed = seed;
-    h->mt_valid = true;
+    hipLaunchKernelGGL(k_mt64_seed, dim3(1), dim3(64), 0, st, r.mt.p, (uint64_t)(int64_t)seed);
+    r.mt_pos = 0;
+    r.mt_seed = seed;
+    r.mt_valid = true;
   }
   // far targets (a rank of a multi-GPU bootstrap seeks to its first replicate): GF(2) jump-ahead on
   // the host, ~0.3 s whatever the distance, instead of 2 ns per word on the device
-  if (target - h->mt_pos >= kMtJumpMin && !getenv("MSWEEP_MT_NOJUMP")) {
+  if (target - r.mt_pos >= kMtJumpMin && !getenv("MSWEEP_MT_NOJUMP")) {
     MtState hs;
-    MSW_HIP(hipMemcpyAsync(&hs, h->mt.p, sizeof hs, hipMemcpyDeviceToHost, st));
+    MSW_HIP(hipMemcpyAsync(&hs, r.mt.p, sizeof hs, hipMemcpyDeviceToHost, st));
     MSW_HIP(hipStreamSynchronize(st));
     std::array<uint64_t, mtjump::kN> w;
     std::copy(hs.mt, hs.mt + mtjump::kN, w.begin());
-    mtjump::jump(w, target - h->mt_pos);
+    mtjump::jump(w, target - r.mt_pos);
     std::copy(w.begin(), w.end(), hs.mt);
-    hs.produced += target - h->mt_pos;
-    MSW_HIP(hipMemcpyAsync(h->mt.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+    hs.produced += target - r.mt_pos;
+    MSW_HIP(hipMemcpyAsync(r.mt.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));
     MSW_HIP(hipStreamSynchronize(st));
-    h->mt_pos = target;
+    r.mt_pos = target;
   }
-  if (h->mt_pos < target) {
-    hipLaunchKernelGGL(k_mt64, dim3(1), dim3(256), 0, st, h->mt.p, target - h->mt_pos, (uint64_t)0,
+  if (r.mt_pos < target) {
+    hipLaunchKernelGGL(k_mt64, dim3(1), dim3(256), 0, st, r.mt.p, target - r.mt_pos, (uint64_t)0,
                        (uint64_t *)nullptr);
-    h->mt_pos = target;
+    r.mt_pos = target;
   }
   MSW_HIP(hipGetLastError());
 }
 
-// Replicate b of the stream into `counts` (device, uint32[E]), enqueued on stream `st`.
-void resample_one(msw_core *h, size_t E, int32_t seed, size_t draws, size_t b, uint32_t *counts,
-                  hipStream_t st) {
+// Replicate b of the stream into `counts` (device, uint32[E]), enqueued on stream `st`; cp: the handle's table.
+void resample_one(Resampler &r, const double *cp, int n_cu, size_t E, int32_t seed, size_t draws, size_t b,
+                  uint32_t *counts, hipStream_t st) {
   MSW_HIP(hipMemsetAsync(counts, 0, E * sizeof(uint32_t), st));
   if (E == 1) {
     // a single weight: libstdc++ returns 0 without consuming a random number
-    h->one_count = (uint32_t)draws;
-    MSW_HIP(hipMemcpyAsync(counts, &h->one_count, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    r.one_count = (uint32_t)draws;
+    MSW_HIP(hipMemcpyAsync(counts, &r.one_count, sizeof(uint32_t), hipMemcpyHostToDevice, st));
     return;
   }
-  mt_seek(h, seed, (uint64_t)b * draws, st);
-  h->mtwords.alloc(draws);
-  hipLaunchKernelGGL(k_mt64, dim3(1), dim3(256), 0, st, h->mt.p, (uint64_t)0, (uint64_t)draws, h->mtwords.p);
-  h->mt_pos += draws;
-  const unsigned nb = (unsigned)std::min<size_t>((draws + 255) / 256, (size_t)h->n_cu * 16);
-  hipLaunchKernelGGL(k_resample, dim3(std::max(nb, 1u)), dim3(256), 0, st, h->mtwords.p, (uint64_t)draws,
-                     h->cp.p, (uint32_t)E, counts);
+  mt_seek(r, seed, (uint64_t)b * draws, st);
+  r.mtwords.alloc(draws);
+  hipLaunchKernelGGL(k_mt64, dim3(1), dim3(256), 0, st, r.mt.p, (uint64_t)0, (uint64_t)draws, r.mtwords.p);
+  r.mt_pos += draws;
+  const unsigned nb = (unsigned)std::min<size_t>((draws + 255) / 256, (size_t)n_cu * 16);
+  hipLaunchKernelGGL(k_resample, dim3(std::max(nb, 1u)), dim3(256), 0, st, r.mtwords.p, (uint64_t)draws,
+                     cp, (uint32_t)E, counts);
   MSW_HIP(hipGetLastError());
 }
 
@@ -122,92 +122,59 @@ void resample_impl(msw_core *h, const uint32_t *ec_counts, size_t E, int32_t see
   if (!ec_counts || !counts_out) throw Fail("msw_core_resample_counts: null argument");
   check_bootstrap_args(E, draws, rep_begin, rep_end);
   upload_cp(h, ec_counts, E);
-  h->bcounts.alloc(E);
+  Resampler &r = h->resampler;
+  r.bcounts.alloc(E);
   for (size_t b = rep_begin; b < rep_end; ++b) {
-    resample_one(h, E, seed, draws, b, h->bcounts.p, h->stream);
-    MSW_HIP(hipMemcpyAsync(counts_out + (b - rep_begin) * E, h->bcounts.p, E * sizeof(uint32_t),
+    resample_one(r, h->cp.p, h->n_cu, E, seed, draws, b, r.bcounts.p, h->stream);
+    MSW_HIP(hipMemcpyAsync(counts_out + (b - rep_begin) * E, r.bcounts.p, E * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, h->stream));
     MSW_HIP(hipStreamSynchronize(h->stream));
   }
 }
 
-// `dst` becomes a second solver state on the likelihood resident in `src`: the read-only buffers are
-// borrowed, the solve state and the streams are its own.
-void share_likelihood(msw_core *dst, msw_core *src) {
-  dst->device = src->device;
-  dst->n_cu = src->n_cu;
-  if (!dst->stream) MSW_HIP(hipStreamCreateWithFlags(&dst->stream, hipStreamNonBlocking));
-  dst->flavor = src->flavor;
-  dst->G = src->G, dst->E = src->E, dst->n_lut = src->n_lut, dst->nslices = src->nslices, dst->n_long = src->n_long;
-  dst->nnz = src->nnz, dst->nslots = src->nslots;
-  dst->enc = src->enc, dst->glds = src->glds, dst->tlds = src->tlds, dst->gmodeB = src->gmodeB;
-  dst->enc_shift = src->enc_shift, dst->enc_mask = src->enc_mask, dst->enc_bhi = src->enc_bhi, dst->enc_bhiA = src->enc_bhiA;
-  dst->enc_shiftH = src->enc_shiftH, dst->enc_maskH = src->enc_maskH;
-  dst->n_tab_lds = src->n_tab_lds;
-  dst->cls = src->cls;
-  dst->slice_hot.borrow(src->slice_hot);
-  dst->n_area = src->n_area, dst->long_row = src->long_row, dst->logzi = src->logzi;
-  dst->rows_over8 = src->rows_over8, dst->passB_rc8 = src->passB_rc8;
-  dst->nblk = src->nblk, dst->nblk_dense = src->nblk_dense, dst->nreg = src->nreg;
-  dst->area_slot.borrow(src->area_slot);
-  dst->lut_area.borrow(src->lut_area);
-  dst->trange.borrow(src->trange);
-  dst->rec.borrow(src->rec);
-  dst->slice_off.borrow(src->slice_off);
-  dst->long_ptr.borrow(src->long_ptr);
-  dst->rec_long.borrow(src->rec_long);
-  dst->perm.borrow(src->perm);
-  dst->lut.borrow(src->lut);
-  dst->Lt.borrow(src->Lt);
-  dst->cp.borrow(src->cp);
-  dst->opts = src->opts;
-  dst->have_solution = dst->prepared = false;
-  dst->mt_valid = false;
-  alloc_solve_state(dst);
-}
-
-// Replicates [b0, b1) on solver state c: resampling of replicate b + 1 (sequential Mersenne-Twister
-// stream, one workgroup) runs on a second stream underneath the solve of replicate b; two count
+// Replicates [b0, b1) on worker w, on the likelihood resident in h: resampling of replicate b + 1 (sequential
+// Mersenne-Twister stream, one workgroup) runs on a second stream underneath the solve of replicate b; two count
 // buffers in ping-pong.
-void bootstrap_range(msw_core *c, int32_t seed, size_t draws, size_t b0, size_t b1, const double *alpha0, double tol,
-                     size_t max_iters, int algo, int prec, double *theta_out, size_t *iters_out) {
-  MSW_HIP(hipSetDevice(c->device));
-  const size_t E = c->E, G = c->G;
-  MSW_HIP(hipMemcpyAsync(c->alpha0.p, alpha0, G * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  // (each on its own: the likelihood build makes the stream and the first event for its side upload, host_build.inc)
-  if (!c->stream2) MSW_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-  for (auto &ev : c->ev_counts)
+void bootstrap_range(const msw_core &h, Worker &w, int32_t seed, size_t draws, size_t b0, size_t b1, const double *alpha0,
+                     double tol, size_t max_iters, int algo, int prec, double *theta_out, size_t *iters_out) {
+  MSW_HIP(hipSetDevice(h.device));
+  const Resident &L = h.lik;
+  Solver &s = w.s;
+  Resampler &r = w.r;
+  const size_t E = L.E, G = L.G;
+  MSW_HIP(hipMemcpyAsync(s.alpha0.p, alpha0, G * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  if (!r.stream2) MSW_HIP(hipStreamCreateWithFlags(&r.stream2, hipStreamNonBlocking));
+  for (auto &ev : r.ev_counts)
     if (!ev) MSW_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  c->bcounts.alloc(E);
-  c->bcounts2.alloc(E);
-  uint32_t *buf[2] = {c->bcounts.p, c->bcounts2.p};
+  r.bcounts.alloc(E);
+  r.bcounts2.alloc(E);
+  uint32_t *buf[2] = {r.bcounts.p, r.bcounts2.p};
   if (b0 < b1) {
-    MSW_HIP(hipStreamSynchronize(c->stream));
-    resample_one(c, E, seed, draws, b0, buf[0], c->stream2);
-    MSW_HIP(hipEventRecord(c->ev_counts[0], c->stream2));
+    MSW_HIP(hipStreamSynchronize(s.stream));
+    resample_one(r, h.cp.p, h.n_cu, E, seed, draws, b0, buf[0], r.stream2);
+    MSW_HIP(hipEventRecord(r.ev_counts[0], r.stream2));
   }
   for (size_t b = b0; b < b1; ++b) {
     const int cur = (int)((b - b0) & 1);
-    MSW_HIP(hipStreamWaitEvent(c->stream, c->ev_counts[cur], 0));
-    prepare_inputs(c, nullptr, buf[cur], nullptr);  // synchronises: buf[cur] is free afterwards
+    MSW_HIP(hipStreamWaitEvent(s.stream, r.ev_counts[cur], 0));
+    prepare_inputs(L, s, nullptr, buf[cur], nullptr);  // synchronises: buf[cur] is free afterwards
     if (b + 1 < b1) {
-      resample_one(c, E, seed, draws, b + 1, buf[cur ^ 1], c->stream2);
-      MSW_HIP(hipEventRecord(c->ev_counts[cur ^ 1], c->stream2));
+      resample_one(r, h.cp.p, h.n_cu, E, seed, draws, b + 1, buf[cur ^ 1], r.stream2);
+      MSW_HIP(hipEventRecord(r.ev_counts[cur ^ 1], r.stream2));
     }
     size_t it = 0;
     try {
-      run_impl(c, tol, max_iters, algo, prec, theta_out + b * G, &it, nullptr);
+      run_impl(L, s, tol, max_iters, algo, prec, theta_out + b * G, &it, nullptr);
     } catch (const NumericFail &) {
       // a replicate whose solve fails NUMERICALLY (likelihood underflow, non-finite bound: the reference returns
       // NaN weights there) is reported as a row of NaN; the other replicates are unaffected.  Everything else --
       // device errors, internal errors, bad arguments (validated before the workers start) -- propagates.
       std::fill(theta_out + b * G, theta_out + (b + 1) * G, std::numeric_limits<double>::quiet_NaN());
-      it = (size_t)c->sc_host->iter;
-      c->in_collective = false;  // (the throw skipped run_impl's CollectiveScope::leave)
+      it = (size_t)s.sc_host->iter;
     }
     if (iters_out) iters_out[b] = it;
   }
-  MSW_HIP(hipStreamSynchronize(c->stream2));
+  MSW_HIP(hipStreamSynchronize(r.stream2));
 }
 
 // How many replicates to run at a time.  Up to a few million reads an iteration is a chain of short
@@ -216,8 +183,8 @@ void bootstrap_range(msw_core *c, int32_t seed, size_t draws, size_t b0, size_t 
 // fill every CU (one 1024-thread workgroup with 150 KB of LDS each) and a second replicate only gets in their
 // way: 43.9 ms per replicate one at a time, 49.3 with two in flight, 50.4 with four
 // (tools/bootstrap_streams_timing.py, round 2; the next replicate's resampling runs under the solve either way).
-int bootstrap_streams(const msw_core *h, size_t n_reps) {
-  int n = h->nnz < 30000000ull || h->flavor != 0 ? 4 : 1;
+int bootstrap_streams(const Resident &L, size_t n_reps) {
+  int n = L.nnz < 30000000ull || L.flavor != 0 ? 4 : 1;
   if (const char *e = getenv("MSWEEP_BOOTSTRAP_STREAMS")) n = std::max(1, std::min(16, atoi(e)));
   return (int)std::min<size_t>((size_t)n, std::max<size_t>(n_reps, 1));
 }
@@ -225,40 +192,45 @@ int bootstrap_streams(const msw_core *h, size_t n_reps) {
 void bootstrap_impl(msw_core *h, const uint32_t *ec_counts, int32_t seed, size_t draws, size_t rep_begin,
                     size_t rep_end, const double *alpha0, double tol, size_t max_iters, int algo,
                     int prec, double *theta_out, size_t *iters_out) {
-  if (h->flavor < 0) throw Fail("msw_core_bootstrap: no likelihood resident");
+  const Resident &L = h->lik;
+  if (L.flavor < 0) throw Fail("msw_core_bootstrap: no likelihood resident");
   if (h->comm)
     throw Fail("msw_core_bootstrap: replicates shard over GPUs as whole solves (rep_begin / rep_end, or "
                "msw_core_bootstrap_dist); detach the EC-sharding communicator first");
   if (!ec_counts || !alpha0 || !theta_out) throw Fail("msw_core_bootstrap: null argument");
-  const size_t E = h->E, G = h->G;
+  const size_t E = L.E, G = L.G;
   check_bootstrap_args(E, draws, rep_begin, rep_end);
-  validate_solve(h, max_iters, algo, prec);  // bad arguments fail the whole call (never a table of NaN)
+  validate_solve(max_iters, algo, prec);  // bad arguments fail the whole call (never a table of NaN)
   const auto t_begin = std::chrono::steady_clock::now();
   upload_cp(h, ec_counts, E);
   const auto t_table = std::chrono::steady_clock::now();
   const size_t n_reps = rep_end - rep_begin;
-  const int n_ctx = bootstrap_streams(h, n_reps);
-  // contiguous blocks of replicates per solver state, like ranks of a multi-GPU run (each seeks --
-  // or jumps -- to its first replicate of the one sequential stream once)
-  // Every replicate runs on a solver state of its own that borrows the resident likelihood: the
-  // primary handle keeps the solution of the un-resampled estimate, so msw_core_gamma / msw_core_trace
-  // after the bootstrap still describe it (the reference writes those probabilities, src/mSWEEP.cpp:437-493).
-  std::vector<msw_core *> ctx;
-  while ((int)h->clones.size() < n_ctx) h->clones.emplace_back(new msw_core);
+  const int n_ctx = bootstrap_streams(L, n_reps);
+  // contiguous blocks of replicates per worker, like ranks of a multi-GPU run (each seeks -- or jumps -- to its
+  // first replicate of the one sequential stream once)
+  // Every replicate runs on a worker's solver: the handle's own solver keeps the solution of the un-resampled
+  // estimate, so msw_core_gamma / msw_core_trace after the bootstrap still describe it (the reference writes those
+  // probabilities, src/mSWEEP.cpp:437-493).  Of the handle's settings a worker takes the solver options only: the
+  // replicates solve to tol, unprofiled and untraced, whatever fixed_iters, profiling and trace_theta say.
+  while ((int)h->workers.size() < n_ctx) h->workers.emplace_back(new Worker(h->n_cu));
   for (int i = 0; i < n_ctx; ++i) {
-    share_likelihood(h->clones[i].get(), h);
-    h->clones[i]->trace_theta = 0;
-    ctx.push_back(h->clones[i].get());
+    Worker &w = *h->workers[i];
+    w.s.opts = h->solver.opts;
+    w.s.fixed_iters = w.s.profiling = false;
+    w.s.trace_theta = 0;
+    w.r.mt_valid = false;
+    alloc_solve_state(L, w.s);
   }
   MSW_HIP(hipStreamSynchronize(h->stream));
   double *theta0 = theta_out - rep_begin * G;  // rows are indexed by replicate below
   size_t *iters0 = iters_out ? iters_out - rep_begin : nullptr;
   std::vector<std::string> errs(n_ctx);
   std::vector<std::thread> workers;
+  const msw_core &shared = *h;  // what the workers share (the resident likelihood, the table): read-only
   auto work = [&](int i) {
     const size_t b0 = rep_begin + n_reps * i / n_ctx, b1 = rep_begin + n_reps * (i + 1) / n_ctx;
     try {
-      bootstrap_range(ctx[i], seed, draws, b0, b1, alpha0, tol, max_iters, algo, prec, theta0, iters0);
+      bootstrap_range(shared, *h->workers[i], seed, draws, b0, b1, alpha0, tol, max_iters, algo, prec, theta0, iters0);
     } catch (const std::exception &ex) {
       errs[i] = ex.what();
       (void)hipGetLastError();
@@ -287,7 +259,7 @@ void bootstrap_dist_impl(msw_core *h, msw_comm *comm, const uint32_t *ec_counts,
                          double *theta_out, size_t *iters_out) {
   if (!comm) throw Fail("msw_core_bootstrap_dist: null communicator");
   if (!theta_out) throw Fail("msw_core_bootstrap_dist: null output");
-  const size_t P = (size_t)comm->size(), r = (size_t)comm->rank(), G = h->G;
+  const size_t P = (size_t)comm->size(), r = (size_t)comm->rank(), G = h->lik.G;
   const size_t b0 = n_reps * r / P, b1 = n_reps * (r + 1) / P;
   // a rank's message: its rows {theta, iteration count}, then ONE status word -- a rank whose block fails still
   // takes part in the all-gather (its peers would wait in it for ever otherwise) and every rank learns of it
@@ -309,7 +281,7 @@ void bootstrap_dist_impl(msw_core *h, msw_comm *comm, const uint32_t *ec_counts,
       (void)hipGetLastError();
       mine[msg - 1] = 1.0;
     }
-  } else if (h->flavor < 0 || !ec_counts || !alpha0) {
+  } else if (h->lik.flavor < 0 || !ec_counts || !alpha0) {
     my_err = "msw_core_bootstrap_dist: no likelihood resident or null argument";
     mine[msg - 1] = 1.0;
   }

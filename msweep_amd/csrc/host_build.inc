@@ -24,6 +24,7 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
                            size_t G, const uint64_t *ec_counts, double q, double e, double zi,
                            size_t min_hits, size_t *n_groups_out, uint8_t *mask_out, double *logc_out,
                            bool on_device, uint64_t dev_hits) {
+  Resident &L = h->lik;
   // on_device: ec_tptr / ec_targets / ec_counts are DEVICE pointers (msw_alignment_read_device) and dev_hits =
   // ec_tptr[E]; they are read where they lie
   // EC-sharded build (a communicator is attached): a rank whose OWN block is bad -- arguments, ec_tptr, target ids,
@@ -38,7 +39,7 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
       if (!my_err.empty()) throw Fail(my_err);
       return;
     }
-    CollectiveScope cs(h);
+    CollectiveScope cs(&h->in_collective);
     const unsigned long long flag = my_err.empty() ? 0ull : 1ull;
     unsigned long long total = 0;
     d_status.alloc(1);
@@ -69,14 +70,17 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   // The multiplicities (8 E bytes: 7 ms of PCIe at cfg5) are first needed by K2: they travel on the handle's second
   // stream while the first pass of K1 runs on `st`.  The guard drains that stream on every way out: the copy reads
   // the caller's buffer.
-  if (!h->stream2) MSW_HIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-  if (!h->ev_counts[0]) MSW_HIP(hipEventCreateWithFlags(&h->ev_counts[0], hipEventDisableTiming));
+  if (!h->resampler.stream2) MSW_HIP(hipStreamCreateWithFlags(&h->resampler.stream2, hipStreamNonBlocking));
+  if (!h->resampler.ev_counts[0]) MSW_HIP(hipEventCreateWithFlags(&h->resampler.ev_counts[0], hipEventDisableTiming));
   struct DrainGuard {
     hipStream_t s;
     ~DrainGuard() { (void)hipStreamSynchronize(s); }
-  } drain_side{h->stream2};
-  DevBuf<uint64_t> d_tptr, d_ecc, gt;
-  DevBuf<uint32_t> d_targets, d_tgroup, d_mid, d_long, d_ctr, d_rowptr, d_grp, d_cnt, tot;
+  } drain_side{h->resampler.stream2};
+  DevBuf<uint64_t> tptr_up, ecc_up, gt;
+  DevBuf<uint32_t> targets_up, d_tgroup, d_mid, d_long, d_ctr, d_rowptr, d_grp, d_cnt, tot;
+  // the pseudoalignment on the device: the caller's arrays (on_device) or the copies uploaded below
+  const uint64_t *d_tptr = ec_tptr, *d_ecc = ec_counts;
+  const uint32_t *d_targets = ec_targets;
   uint64_t nnz = 0;
   local_stage([&] {
   if (!ec_tptr || !target_group || !group_sizes || !ec_counts) throw Fail("msw_core_build_likelihood: null argument");
@@ -95,22 +99,17 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   for (size_t g = 0; g < G; ++g)
     if (group_sizes[g] == 0 || group_sizes[g] > 0x7fffffffull) throw Fail("msw_core_build_likelihood: bad group size");
   reset_likelihood(h);
-  auto view = [](auto &buf, const auto *p, size_t n) {  // (released, never freed: DevBuf::borrowed)
-    buf.release();
-    buf.p = const_cast<std::remove_const_t<std::remove_pointer_t<decltype(p)>> *>(p);
-    buf.n = n;
-    buf.borrowed = true;
-  };
-  if (on_device) {
-    view(d_tptr, ec_tptr, E + 1);
-    view(d_targets, ec_targets, ntot);
-    view(d_ecc, ec_counts, E);
-  } else {
-    d_tptr.upload(ec_tptr, E + 1, st);
-    d_targets.upload(ec_targets, ntot, st);
+  if (!on_device) {
+    tptr_up.upload(ec_tptr, E + 1, st);
+    targets_up.upload(ec_targets, ntot, st);
+    d_tptr = tptr_up.p;
+    d_targets = targets_up.p;
   }
   d_tgroup.upload(target_group, T, st);
-  if (!on_device) d_ecc.alloc(E);
+  if (!on_device) {
+    ecc_up.alloc(E);
+    d_ecc = ecc_up.p;
+  }
   d_mid.alloc(E);   // ECs of 17..64 hits / of more than 64: listed by the first pass of K1
   d_long.alloc(E);
   d_ctr.alloc(kBuildCtrs);
@@ -121,13 +120,13 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
 
   // ---- K1: count distinct groups per EC, scan, emit (group, count) ----------------------------
   const unsigned nbt = (unsigned)std::min<size_t>((E + 255) / 256, (size_t)h->n_cu * 32);
-  hipLaunchKernelGGL(k_ec_groups_thread<false>, dim3(nbt), dim3(256), 0, st, d_tptr.p, d_targets.p, d_tgroup.p, (uint32_t)E,
+  hipLaunchKernelGGL(k_ec_groups_thread<false>, dim3(nbt), dim3(256), 0, st, d_tptr, d_targets, d_tgroup.p, (uint32_t)E,
                      (uint32_t)T, ntot, d_rowptr.p, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                      d_mid.p, d_long.p, d_ctr.p);
   MSW_HIP(hipGetLastError());
-  if (!on_device) d_ecc.upload(ec_counts, E, h->stream2);  // under the kernel just launched
-  MSW_HIP(hipEventRecord(h->ev_counts[0], h->stream2));
-  MSW_HIP(hipStreamWaitEvent(st, h->ev_counts[0], 0));  // (whatever follows on `st` sees the counts)
+  if (!on_device) ecc_up.upload(ec_counts, E, h->resampler.stream2);  // under the kernel just launched
+  MSW_HIP(hipEventRecord(h->resampler.ev_counts[0], h->resampler.stream2));
+  MSW_HIP(hipStreamWaitEvent(st, h->resampler.ev_counts[0], 0));  // (whatever follows on `st` sees the counts)
   uint32_t ctr[kBuildCtrs] = {};
   auto read_ctr = [&] {
     MSW_HIP(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
@@ -148,12 +147,12 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
     MSW_HIP(hipFuncSetAttribute((const void *)k_ec_groups_long<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
   }
   if (n_mid)
-    hipLaunchKernelGGL(k_ec_groups_wave<false>, dim3(nbw), dim3(256), 0, st, d_mid.p, n_mid, d_tptr.p, d_targets.p,
+    hipLaunchKernelGGL(k_ec_groups_wave<false>, dim3(nbw), dim3(256), 0, st, d_mid.p, n_mid, d_tptr, d_targets,
                        d_tgroup.p, (uint32_t)T, d_rowptr.p, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                        (uint32_t *)nullptr, d_ctr.p);
   if (n_long)
-    hipLaunchKernelGGL(k_ec_groups_long<false>, dim3(nbl), dim3(256), lds_long, st, d_long.p, n_long, d_tptr.p,
-                       d_targets.p, d_tgroup.p, (uint32_t)G, (uint32_t)T, hist_lds ? nullptr : scratch.p, d_rowptr.p,
+    hipLaunchKernelGGL(k_ec_groups_long<false>, dim3(nbl), dim3(256), lds_long, st, d_long.p, n_long, d_tptr,
+                       d_targets, d_tgroup.p, (uint32_t)G, (uint32_t)T, hist_lds ? nullptr : scratch.p, d_rowptr.p,
                        (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, d_ctr.p);
   MSW_HIP(hipGetLastError());
   nnz = device_scan_u32(h, d_rowptr.p, E + 1, tot, gt);
@@ -162,15 +161,15 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   if (nnz >= 0xffffffffull) throw Fail("msw_core_build_likelihood: more than 2^32-1 nonzero cells");
   d_grp.alloc(nnz);
   d_cnt.alloc(nnz);
-  hipLaunchKernelGGL(k_ec_groups_thread<true>, dim3(nbt), dim3(256), 0, st, d_tptr.p, d_targets.p, d_tgroup.p, (uint32_t)E,
+  hipLaunchKernelGGL(k_ec_groups_thread<true>, dim3(nbt), dim3(256), 0, st, d_tptr, d_targets, d_tgroup.p, (uint32_t)E,
                      (uint32_t)T, ntot, (uint32_t *)nullptr, d_rowptr.p, d_grp.p, d_cnt.p, (uint32_t *)nullptr,
                      (uint32_t *)nullptr, d_ctr.p);
   if (n_mid)
-    hipLaunchKernelGGL(k_ec_groups_wave<true>, dim3(nbw), dim3(256), 0, st, d_mid.p, n_mid, d_tptr.p, d_targets.p,
+    hipLaunchKernelGGL(k_ec_groups_wave<true>, dim3(nbw), dim3(256), 0, st, d_mid.p, n_mid, d_tptr, d_targets,
                        d_tgroup.p, (uint32_t)T, (uint32_t *)nullptr, d_rowptr.p, d_grp.p, d_cnt.p, d_ctr.p);
   if (n_long)
-    hipLaunchKernelGGL(k_ec_groups_long<true>, dim3(nbl), dim3(256), lds_long, st, d_long.p, n_long, d_tptr.p,
-                       d_targets.p, d_tgroup.p, (uint32_t)G, (uint32_t)T, hist_lds ? nullptr : scratch.p,
+    hipLaunchKernelGGL(k_ec_groups_long<true>, dim3(nbl), dim3(256), lds_long, st, d_long.p, n_long, d_tptr,
+                       d_targets, d_tgroup.p, (uint32_t)G, (uint32_t)T, hist_lds ? nullptr : scratch.p,
                        (uint32_t *)nullptr, d_rowptr.p, d_grp.p, d_cnt.p, d_ctr.p);
   MSW_HIP(hipGetLastError());
   if (h->comm) MSW_HIP(hipStreamSynchronize(st));  // sharded: a device fault of this stage surfaces inside it
@@ -194,7 +193,7 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
     for (uint32_t g0 = 0; g0 < G; g0 += kHitsGroups) {
       const uint32_t ng = (uint32_t)std::min<size_t>(kHitsGroups, G - g0);
       hipLaunchKernelGGL(k_group_hits, dim3((unsigned)std::min<size_t>((E + 1023) / 1024, (size_t)h->n_cu)), dim3(1024),
-                         ng * sizeof(unsigned long long), st, d_rowptr.p, d_grp.p, (uint32_t)E, d_ecc.p, g0, ng, d_hits.p);
+                         ng * sizeof(unsigned long long), st, d_rowptr.p, d_grp.p, (uint32_t)E, d_ecc, g0, ng, d_hits.p);
     }
     // EC-sharded build (a communicator is attached: this handle holds one rank's block of ECs): the hits of a
     // group are summed over ALL ECs (include/Likelihood.hpp:146-163) -- one all-reduce of G integers, after
@@ -265,18 +264,18 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   d_csize.upload(class_size.data(), class_size.size(), st);
   d_lutoff.upload(lut_off.data(), Gk, st);
   d_ksize.upload(ksize.data(), Gk, st);
-  h->lut.alloc(n_lut);
+  L.lut.alloc(n_lut);
   hipLaunchKernelGGL(k_lut_build, dim3((unsigned)((n_lut + 255) / 256)), dim3(256), 0, st, d_csize.p,
-                     (uint32_t)class_size.size(), (uint32_t)ld, q, e, zi, h->lut.p);
+                     (uint32_t)class_size.size(), (uint32_t)ld, q, e, zi, L.lut.p);
   d_idx.alloc(nnz);
   d_bad.alloc(1);
   MSW_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), st));
   if (nnz)
     hipLaunchKernelGGL(k_cell_lutidx, dim3((unsigned)std::min<uint64_t>((nnz + 255) / 256, (uint64_t)h->n_cu * 32)),
                        dim3(256), 0, st, d_grp.p, d_cnt.p, nnz, d_lutoff.p, d_ksize.p, d_idx.p, d_bad.p);
-  DevBuf<double> &d_logc = h->logc_res;  // stays resident: msw_core_solve(logc = NULL) uses it
+  DevBuf<double> &d_logc = L.logc_res;  // stays resident: msw_core_solve(logc = NULL) uses it
   d_logc.alloc(E);
-  hipLaunchKernelGGL(k_log_counts, dim3(nbe), dim3(256), 0, st, d_ecc.p, (uint32_t)E, d_logc.p);
+  hipLaunchKernelGGL(k_log_counts, dim3(nbe), dim3(256), 0, st, d_ecc, (uint32_t)E, d_logc.p);
   MSW_HIP(hipGetLastError());
 
   // ---- pack into SELL-64: on the device (pack_kernels.hpp); MSWEEP_HOST_PACK=1 takes the CSR to the
@@ -287,11 +286,11 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   MSW_HIP(hipStreamSynchronize(st));
   tm.mark("K0 table, slots, log counts");
   if (bad) throw Fail("msw_core_build_likelihood: an EC hits more sequences of a group than the group holds");
-  h->G = (uint32_t)Gk;
-  h->E = (uint32_t)E;
-  h->nnz = nnz;
-  h->n_lut = (uint32_t)n_lut;
-  h->logzi = std::log(zi);
+  L.G = (uint32_t)Gk;
+  L.E = (uint32_t)E;
+  L.nnz = nnz;
+  L.n_lut = (uint32_t)n_lut;
+  L.logzi = std::log(zi);
   if (getenv("MSWEEP_HOST_PACK")) {
     std::vector<uint32_t> rp(E + 1), hg(nnz + 1), hi(nnz + 1);
     MSW_HIP(hipMemcpyAsync(rp.data(), d_rowptr.p, (E + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -305,7 +304,7 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
     sell_from_device(h, d_rowptr.p, d_grp.p, d_idx.p);
   }
   tm.mark("pack (total)");
-  h->have_logc_res = true;
+  L.have_logc_res = true;
   });  // local stage 2
   if (n_groups_out) *n_groups_out = Gk;
   if (mask_out) std::memcpy(mask_out, mask.data(), G);

@@ -14,7 +14,8 @@ constexpr size_t kCompressSample = 4096;
 // force: the matrix has more groups than the dense sweeps take (dense_kernels.hpp: 8192) -- it is re-expressed
 // whatever its shape (most frequent sampled value as the background, every other cell listed with a slot of its
 // own), up to 2^28 listed cells.
-bool compress_dense(msw_core *h, const double *L, size_t ld, const double *stage, size_t G, size_t E, bool force) {
+bool compress_dense(msw_core *h, const double *Lm, size_t ld, const double *stage, size_t G, size_t E, bool force) {
+  Resident &L = h->lik;
   const char *sw = getenv("MSWEEP_DENSE_COMPRESS");  // developer switch: 0 = always the dense sweeps
   if (sw && atoi(sw) == 0 && !force) return false;
   if (G > 0x7fffffffull) return false;
@@ -29,7 +30,7 @@ bool compress_dense(msw_core *h, const double *L, size_t ld, const double *stage
       x = x * 6364136223846793005ull + 1442695040888963407ull;
       const size_t c = cells <= kCompressSample ? i : (size_t)((x >> 11) % cells);
       uint64_t v;
-      std::memcpy(&v, &L[(c / E) * ld + c % E], sizeof v);
+      std::memcpy(&v, &Lm[(c / E) * ld + c % E], sizeof v);
       const uint32_t k = ++seen[v];
       if (k > best) {
         best = k;
@@ -102,23 +103,23 @@ bool compress_dense(msw_core *h, const double *L, size_t ld, const double *stage
       MSW_HIP(hipGetLastError());
     }
   }
-  h->G = (uint32_t)G;
-  h->E = (uint32_t)E;
-  h->nnz = nnz;
-  std::memcpy(&h->logzi, &bg, sizeof bg);
+  L.G = (uint32_t)G;
+  L.E = (uint32_t)E;
+  L.nnz = nnz;
+  std::memcpy(&L.logzi, &bg, sizeof bg);
   if (value_records) {
-    h->n_lut = 1;
-    h->lut.alloc(1);
-    MSW_HIP(hipMemcpyAsync(h->lut.p, &h->logzi, sizeof(double), hipMemcpyHostToDevice, st));
+    L.n_lut = 1;
+    L.lut.alloc(1);
+    MSW_HIP(hipMemcpyAsync(L.lut.p, &L.logzi, sizeof(double), hipMemcpyHostToDevice, st));
     sell_from_device(h, d_rowptr.p, d_grp.p, d_idx.p, reinterpret_cast<const double *>(d_lut.p));  // synchronises
     return true;
   }
-  h->n_lut = (uint32_t)std::max<uint64_t>(n_values, 1);
-  h->lut.alloc(h->n_lut);
+  L.n_lut = (uint32_t)std::max<uint64_t>(n_values, 1);
+  L.lut.alloc(L.n_lut);
   if (n_values)
-    MSW_HIP(hipMemcpyAsync(h->lut.p, d_lut.p, n_values * sizeof(double), hipMemcpyDeviceToDevice, st));
+    MSW_HIP(hipMemcpyAsync(L.lut.p, d_lut.p, n_values * sizeof(double), hipMemcpyDeviceToDevice, st));
   else
-    MSW_HIP(hipMemcpyAsync(h->lut.p, &h->logzi, sizeof(double), hipMemcpyHostToDevice, st));
+    MSW_HIP(hipMemcpyAsync(L.lut.p, &L.logzi, sizeof(double), hipMemcpyHostToDevice, st));
   sell_from_device(h, d_rowptr.p, d_grp.p, d_idx.p);  // synchronises
   return true;
 }

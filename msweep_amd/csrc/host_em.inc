@@ -3,40 +3,40 @@
 // (em_f32_layout_ok) and the fp64 kernels elsewhere -- msw_timing::em_float_kernels reports which.
 namespace {
 
-void run_em(msw_core *h, size_t max_iters, int prec) {
-  const int G = (int)h->G, n_lut = h->n_tab_inline();
-  TraceDev tr{h->tr_bound.p, h->tr_newnorm.p, h->tr_beta.p, h->tr_theta.p, h->tr_reset.p};
-  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, h->stream, h->sc.p, G, n_lut, h->u.p, h->lut_area.p,
-                     h->e.p, h->tabs());
-  launch_tables(h);  // a = 1 throughout: built once, every later call returns at once
-  const bool f32 = prec == MSW_PREC_FLOAT && em_f32_layout_ok(h);
+void run_em(const Resident &L, Solver &s, size_t max_iters, int prec) {
+  const int G = (int)L.G, n_lut = L.n_tab_inline();
+  TraceDev tr{s.tr_bound.p, s.tr_newnorm.p, s.tr_beta.p, s.tr_theta.p, s.tr_reset.p};
+  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, s.stream, s.sc.p, G, n_lut, s.u.p, L.lut_area.p,
+                     s.e.p, s.tabs());
+  launch_tables(L, s);  // a = 1 throughout: built once, every later call returns at once
+  const bool f32 = prec == MSW_PREC_FLOAT && em_f32_layout_ok(L, s);
   struct Flag {  // (launch_passB reads it; cleared on every way out)
-    msw_core *h;
-    ~Flag() { h->em_f32 = false; }
-  } flag{h};
-  h->em_f32 = f32;
-  h->timing.em_float_kernels = f32 ? 1 : 0;
+    Solver &s;
+    ~Flag() { s.em_f32 = false; }
+  } flag{s};
+  s.em_f32 = f32;
+  s.timing.em_float_kernels = f32 ? 1 : 0;
   if (f32) {
-    h->e32.alloc((size_t)G + kSentinels);
-    h->tab32.alloc(std::max<uint32_t>(h->n_area, 1));
-    hipLaunchKernelGGL(k_em_f32_prep, dim3(1), dim3(1024), 0, h->stream, h->sc.p, G, (int)h->n_area, h->lut_area.p, h->e.p,
-                       h->e32.p, h->tab32.p);
+    s.e32.alloc((size_t)G + kSentinels);
+    s.tab32.alloc(std::max<uint32_t>(L.n_area, 1));
+    hipLaunchKernelGGL(k_em_f32_prep, dim3(1), dim3(1024), 0, s.stream, s.sc.p, G, (int)L.n_area, L.lut_area.p, s.e.p,
+                       s.e32.p, s.tab32.p);
   }
   size_t enq = 0;
   while (enq < max_iters) {
     const size_t batch = std::min<size_t>(kIterBatch, max_iters - enq);
     for (size_t b = 0; b < batch; ++b) {
-      launch_passB(h);
-      hipLaunchKernelGGL(k_em_fin, dim3(1), dim3(1024), 0, h->stream, h->sc.p, G, n_lut, fin_npartS(h), fin_partS(h),
-                         h->Nc.p, h->alpha0.p, h->u.p, h->logth.p, h->lut_area.p, h->e.p, h->tabs(), tr,
-                         f32 ? h->e32.p : (float *)nullptr);
+      launch_passB(L, s);
+      hipLaunchKernelGGL(k_em_fin, dim3(1), dim3(1024), 0, s.stream, s.sc.p, G, n_lut, fin_npartS(L, s), fin_partS(L, s),
+                         s.Nc.p, s.alpha0.p, s.u.p, s.logth.p, L.lut_area.p, s.e.p, s.tabs(), tr,
+                         f32 ? s.e32.p : (float *)nullptr);
     }
     MSW_HIP(hipGetLastError());
     enq += batch;
-    poll(h);
-    if (h->sc_host->done) break;
+    poll(s);
+    if (s.sc_host->done) break;
   }
-  // h->logth now holds theta of the last M-step; u = log(theta) stays in h->u for gamma
+  // s.logth now holds theta of the last M-step; u = log(theta) stays in s.u for gamma
 }
 
 }  // namespace

@@ -59,10 +59,9 @@ struct ReaderCtx {
   ReaderCtx &operator=(const ReaderCtx &) = delete;
   template <class T>
   void drop(DevBuf<T> &b) {
-    if (b.p && !b.borrowed) pool->give(b.p);
+    if (b.p) pool->give(b.p);
     b.p = nullptr;
     b.n = 0;
-    b.borrowed = false;
   }
   unsigned char *scratch(size_t bytes) {  // grows, never shrinks
     tmp.alloc(bytes);

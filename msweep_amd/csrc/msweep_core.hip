@@ -45,91 +45,115 @@ constexpr size_t kLdsMax = 160 * 1024;
 constexpr int kIterBatch = 16;
 }  // namespace
 
-struct msw_core {
-  int device = 0;
-  int n_cu = 256;
-  hipStream_t stream = nullptr;
-  std::string err;
-  TextStager text_stage;  // pinned staging of msw_alignment_read_device (host_reader.inc)
-  ReaderPool reader_pool;  // ... and its device memory, kept between calls (reader_kernels.hpp)
+// The handle's parts, by lifetime: the likelihood resident on the device (Resident: written by the
+// build paths only), the state of one solve on it (Solver), the bootstrap's resampling state (Resampler), and what
+// belongs to the handle as a whole (msw_core).  A bootstrap worker is a Solver and a Resampler of its own that
+// solve on the handle's Resident through a const reference.
 
-  // ---- resident likelihood -----------------------------------------------------------
+// shape and layout of the resident likelihood: plain values, so that a new build starts from one assignment
+struct LikShape {
   int flavor = -1;  // -1 none, 0 CSR-of-ECs, 1 dense
   uint32_t G = 0, E = 0, n_lut = 0, nslices = 0, n_long = 0;
   uint64_t nnz = 0, nslots = 0;
   int enc = kEncNarrow;  // record encoding (sell.hpp): narrow byte offsets / wide / index records (hybrid area)
   bool glds = true, tlds = true;
-  int gmodeB = 1;  // k_passB GMODE (sweep_kernels.hpp)
-  uint32_t enc_shift = 0, enc_mask = 0, enc_bhi = 0, enc_bhiA = 0;  // record encoding (sell.hpp)
-  uint32_t enc_shiftH = 0, enc_maskH = 0;               // index records: the rows of a hot segment
-  uint32_t n_area = 0;                                  // 16-byte entries of the slot area
-  uint32_t n_tab_lds = 0;                               // ... of which the LDS images hold (all, the hot head, none)
-  DevBuf<uint8_t> slice_hot;                            // index records: rows of every slice's hot segment
-  SliceClasses cls = {};                                // slice classes: lanes per EC (sell.hpp)
-  bool no_hybrid = false;                               // re-planning without the hybrid area (host_pack.inc: slice geometry beyond 2^27 rows)
-  bool pack_schedule = true;                            // LDS-bank scheduling of the cells at upload (msw_core_set_pack_schedule)
-  bool packed_scheduled = false;                        // ... as the resident likelihood was packed
-  bool wide() const { return enc == kEncWide; }
-  bool hybrid() const { return enc == kEncIndex; }
-  RecDec dec() const { return RecDec{enc_shift, enc_mask, enc_bhi, enc_bhiA, enc_shiftH, enc_maskH}; }
-  uint32_t long_row = kLongRow;                         // ECs with more cells go one per wavefront (reset_likelihood)
-  uint64_t rows_over8 = 0;                              // rows of the slices of more than 8 rows (finish_sell)
-  bool passB_rc8 = false;                               // pass B runs its short-slice instantiation (sweep_kernels.hpp, RC = 8)
-  DevBuf<uint32_t> area_slot;
-  DevBuf<double> lut_area;  // lut[area_slot[i]]: what the per-slot tables are built from, in their order
-  DevBuf<int> tab_built;    // k_tables bookkeeping
-  int n_tab_inline() const { return flavor == 0 && n_area <= (uint32_t)kTabInline ? (int)n_area : 0; }
+  int gmodeB = 1;                // k_passB GMODE (sweep_kernels.hpp)
+  RecDec dec = {};               // record encoding (sell.hpp); shiftH / maskH: index records, the rows of a hot segment
+  uint32_t n_area = 0;           // 16-byte entries of the slot area
+  uint32_t n_tab_lds = 0;        // ... of which the LDS images hold (all, the hot head, none)
+  SliceClasses cls = {};         // slice classes: lanes per EC (sell.hpp)
+  bool packed_scheduled = false;  // LDS-bank scheduling of the cells as the likelihood was packed (msw_core_set_pack_schedule)
+  uint32_t long_row = kLongRow;  // ECs with more cells go one per wavefront (reset_likelihood)
+  uint64_t rows_over8 = 0;       // rows of the slices of more than 8 rows (finish_sell)
+  bool passB_rc8 = false;        // pass B runs its short-slice instantiation (sweep_kernels.hpp, RC = 8)
   double logzi = 0.0;
-  DevBuf<uint32_t> rec, slice_off, long_ptr, rec_long, perm;
-  DevBuf<uint32_t> iperm;  // original EC index -> permuted position (gamma blocks; built on first use)
-  DevBuf<double> lut, Lt;
-  int nblk = 0;      // persistent workgroups of the CSR sweeps
+  int nblk = 0;  // persistent workgroups of the CSR sweeps
   int nblk_dense = 0;
   int nreg = 0;
+  bool have_logc_res = false;  // logc_res holds the log counts msw_core_build_likelihood left
+};
+
+// ---- the likelihood resident on the device --------------------------------------------------------------------
+struct Resident : LikShape {
+  DevBuf<uint32_t> rec, slice_off, long_ptr, rec_long, perm;
+  DevBuf<uint8_t> slice_hot;  // index records: rows of every slice's hot segment
+  DevBuf<uint32_t> area_slot;
+  DevBuf<double> lut_area;  // lut[area_slot[i]]: what the per-slot tables are built from, in their order
+  DevBuf<double> lut, Lt;
+  DevBuf<double> trange;    // {max, min} of the table values (bounds x_i = exp(a T_i) per pass: Scalars::xb)
+  DevBuf<double> logc_res;  // log counts left on the device by msw_core_build_likelihood
+  bool wide() const { return enc == kEncWide; }
+  bool hybrid() const { return enc == kEncIndex; }
+  int n_tab_inline() const { return flavor == 0 && n_area <= (uint32_t)kTabInline ? (int)n_area : 0; }
   // rows of per-workgroup (or per-wave) column-sum partials pass B leaves for k_redfin
   int npart_rows() const { return flavor == 0 ? nblk : (nreg >= 32 ? 4 * nblk_dense : nblk_dense); }
+  // guarded ECs (sell.hpp), CSR flavour: room in a workgroup's list for every EC it can see (its wavefronts take
+  // slices -- and long ECs -- round-robin, SliceStream's stride), and words of a wavefront's bitmap of groups
+  uint32_t guard_cap() const {
+    static_assert(kPassThreads / 64 <= 16 && kPassThreadsB / 64 <= 16, "guard_cap / guard_bits assume <= 16 wavefronts per workgroup");
+    const uint32_t nb0 = (uint32_t)std::max(nblk, 1);
+    return 64u * ((nslices + nb0 - 1) / nb0 + 16u) + (n_long + nb0 - 1) / nb0 + 16u;
+  }
+  uint32_t guard_words() const { return (G + 31u) / 32u; }
+};
 
-  // ---- solve state ---------------------------------------------------------------------
+// ---- the state of one solve on a Resident ----------------------------------------------------------------------
+struct Solver {
+  hipStream_t stream = nullptr;
+  int n_cu = 256;
+  // EC-sharded solve: the handle's communicator and its in_collective flag (guarded()); none for a bootstrap worker
+  msw_comm *const *commp;
+  bool *collective;
+  explicit Solver(msw_comm *const *c = nullptr, bool *coll = nullptr) : commp(c), collective(coll) {}
+  msw_comm *comm() const { return commp ? *commp : nullptr; }
+  // the settings a solve reads
+  SolveOpts opts;  // msw_core_set_option
+  bool profiling = false, fixed_iters = false;
+  size_t trace_theta = 0;
+
   DevBuf<double> cvec, logc_d, alpha0, u, os_u, step_u, w, e, N, Nc, Acc;
   DevBuf<uint8_t> c8, c8s;  // byte image of cvec by EC position / by slice lane (sell.hpp)
-  DevBuf<double> logc_res;  // log counts left on the device by msw_core_build_likelihood
-  bool have_logc_res = false;
   DevBuf<double2> ew, tabA, tabB;  // group table of pass A; per-slot tables of both sweeps (TabDev)
   TabDev tabs() const { return TabDev{tabA.p, tabB.p}; }
+  DevBuf<int> tab_built;    // k_tables bookkeeping
   DevBuf<double> partA, partS, partAcc, partC, partR, totS;
-  // EC-sharded solve: this handle holds one rank's block of ECs (comm.hpp)
   size_t lds_attr[3][80] = {};  // dynamic-LDS limit already granted per sweep instantiation ([2]: pass B's short-slice ones)
-  msw_comm *comm = nullptr;
-  bool in_collective = false;  // a solve / sharded build is under way: a failure now strands the peers (guarded())
   DevBuf<double> commA, commB;  // 1 and G + 4 doubles
   // guarded ECs (sell.hpp): per-workgroup lists, per-wavefront bitmaps, error flag
   DevBuf<uint32_t> guard_list, guard_bits;
   DevBuf<unsigned long long> guard_tail;  // [2 G] the guarded ECs' shares per group, two fixed-point limbs
   DevBuf<int> guard_err;
   DevBuf<unsigned long long> guard_visits;
-  DevBuf<double> trange;  // {max, min} of the table values (bounds x_i = exp(a T_i) per pass: Scalars::xb)
-  uint32_t guard_cap = 0, guard_words = 0;
-  GuardDev guard_view() const {
-    return GuardDev{guard_list.p, guard_bits.p, guard_tail.p, lut_area.p, guard_err.p, guard_visits.p, guard_cap, guard_words};
-  }
   DevBuf<Scalars> sc;
   Scalars *sc_host = nullptr;  // pinned
   DevBuf<double> tr_bound, tr_newnorm, tr_beta, tr_theta;
   DevBuf<int32_t> tr_reset;
-  size_t trace_theta = 0;
   bool have_solution = false;
   bool prepared = false;
   int last_algo = MSW_ALGO_RCG;
-  SolveOpts opts;  // msw_core_set_option
   // EM state
   DevBuf<double> logth;
   DevBuf<float> e32, tab32;  // --emprecision float: e_g and the slot table {x_i - p0} as floats (em_f32_kernels.hpp)
   bool em_f32 = false;       // the EM run under way is served by the fp32 kernels (launch_passB)
 
-  // ---- bootstrap -------------------------------------------------------------------------
-  DevBuf<double> cp;
-  std::vector<uint32_t> cp_counts;  // the EC counts `cp` was made from (host_bootstrap.inc: kept across calls)
-  bool cp_hit = false;              // ... and whether the last call found them again
+  // ---- measurement ---------------------------------------------------------------------------
+  msw_timing timing = {};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> evA, evB, evC;  // pass A, pass B, collectives (sharded solve)
+  size_t evA_used = 0, evB_used = 0, evC_used = 0;
+
+  ~Solver() {
+    if (sc_host) (void)hipHostFree(sc_host);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    for (auto &p : evA) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    for (auto &p : evB) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    for (auto &p : evC) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+  }
+};
+
+// ---- the bootstrap's resampling state of one stream of replicates (host_bootstrap.inc) --------------------------
+struct Resampler {
   DevBuf<uint64_t> mtwords;
   DevBuf<uint32_t> bcounts, bcounts2;
   DevBuf<MtState> mt;
@@ -139,30 +163,47 @@ struct msw_core {
   bool mt_valid = false;
   int32_t mt_seed = 0;
   uint64_t mt_pos = 0;
-  // further solver states on the same resident likelihood (borrowed buffers, streams of their own):
-  // the bootstrap driver runs several replicates at a time (host_bootstrap.inc)
-  std::vector<std::unique_ptr<msw_core>> clones;
-
-  // ---- measurement ---------------------------------------------------------------------------
-  bool profiling = false, fixed_iters = false;
-  msw_timing timing = {};
-  msw_bootstrap_timing btiming = {};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evA, evB, evC;  // pass A, pass B, collectives (sharded solve)
-  size_t evA_used = 0, evB_used = 0, evC_used = 0;
-
-  ~msw_core() {
-    if (sc_host) (void)hipHostFree(sc_host);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    for (auto &p : evA) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &p : evB) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &p : evC) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+  ~Resampler() {
     for (auto &e : ev_counts)
       if (e) (void)hipEventDestroy(e);
     if (stream2) (void)hipStreamDestroy(stream2);
-    if (stream) (void)hipStreamDestroy(stream);
   }
+};
+
+struct Worker {  // a bootstrap worker: replicates on a stream of their own, beside the handle's solver
+  Solver s;
+  Resampler r;
+  explicit Worker(int n_cu) { MSW_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)); s.n_cu = n_cu; }
+  ~Worker() { (void)hipStreamDestroy(s.stream); }
+};
+
+struct msw_core {
+  int device = 0;
+  int n_cu = 256;
+  hipStream_t stream = nullptr;
+  std::string err;
+  TextStager text_stage;  // pinned staging of msw_alignment_read_device (host_reader.inc)
+  ReaderPool reader_pool;  // ... and its device memory, kept between calls (reader_kernels.hpp)
+  // EC-sharded solve: this handle holds one rank's block of ECs (comm.hpp)
+  msw_comm *comm = nullptr;
+  bool in_collective = false;  // a solve / sharded build is under way: a failure now strands the peers (guarded())
+  // build settings
+  bool pack_schedule = true;  // LDS-bank scheduling of the cells at upload (msw_core_set_pack_schedule)
+  bool no_hybrid = false;     // re-planning without the hybrid area (host_pack.inc: slice geometry beyond 2^27 rows)
+
+  Resident lik;
+  DevBuf<uint32_t> iperm;  // original EC index -> permuted position (gamma blocks; built on first use)
+  Solver solver{&comm, &in_collective};  // on the handle's stream
+
+  // ---- bootstrap -------------------------------------------------------------------------
+  DevBuf<double> cp;
+  std::vector<uint32_t> cp_counts;  // the EC counts `cp` was made from (host_bootstrap.inc: kept across calls)
+  bool cp_hit = false;              // ... and whether the last call found them again
+  Resampler resampler;              // msw_core_resample_counts; its stream2 also carries the build's side upload
+  std::vector<std::unique_ptr<Worker>> workers;  // the replicates run on these, several at a time
+  msw_bootstrap_timing btiming = {};
+
+  ~msw_core() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
 namespace {
@@ -177,10 +218,11 @@ struct NumericFail : Fail {
 };
 
 // marks the stretch of a call in which this rank's peers wait for it in collectives
+// (flag: the handle's in_collective; null for a bootstrap worker's solve, which has no peers)
 struct CollectiveScope {
-  msw_core *h;
-  explicit CollectiveScope(msw_core *h_) : h(h_) { h->in_collective = true; }
-  void leave() { h->in_collective = false; }  // on success only: guarded() reads the flag after a throw
+  bool *flag;
+  explicit CollectiveScope(bool *f) : flag(f) { if (flag) *flag = true; }
+  void leave() { if (flag) *flag = false; }  // on success only: guarded() reads the flag after a throw
 };
 
 template <class F>
@@ -212,39 +254,43 @@ std::pair<hipEvent_t, hipEvent_t> &next_pair(std::vector<std::pair<hipEvent_t, h
   return v[used++];
 }
 
-SellDev sell_view(msw_core *h) {
+SellDev sell_view(const Resident &L, const Solver &s) {
   SellDev S;
-  S.rec = h->rec.p;
-  S.slice_off = h->slice_off.p;
-  S.long_ptr = h->long_ptr.p;
-  S.rec_long = h->rec_long.p;
-  S.perm = h->perm.p;
-  S.cvec = h->cvec.p;
-  S.c8 = h->c8.p;
-  S.c8s = h->c8s.p;
-  S.nslices = h->nslices;
-  S.n_long = h->n_long;
-  S.n_ecs = h->E;
-  S.n_groups = h->G;
-  S.n_lut = h->n_lut;
-  S.n_area = h->n_area;
-  S.area_slot = h->area_slot.p;
-  S.shift = h->enc_shift;
-  S.mask = h->enc_mask;
-  S.bhi = h->enc_bhi;
-  S.bhiA = h->enc_bhiA;
-  S.shiftH = h->enc_shiftH;
-  S.maskH = h->enc_maskH;
-  S.n_tab_lds = h->n_tab_lds;
-  S.slice_hot = h->slice_hot.p;
-  S.lut_area = h->lut_area.p;
-  S.cls = h->cls;
+  S.rec = L.rec.p;
+  S.slice_off = L.slice_off.p;
+  S.long_ptr = L.long_ptr.p;
+  S.rec_long = L.rec_long.p;
+  S.perm = L.perm.p;
+  S.cvec = s.cvec.p;
+  S.c8 = s.c8.p;
+  S.c8s = s.c8s.p;
+  S.nslices = L.nslices;
+  S.n_long = L.n_long;
+  S.n_ecs = L.E;
+  S.n_groups = L.G;
+  S.n_lut = L.n_lut;
+  S.n_area = L.n_area;
+  S.area_slot = L.area_slot.p;
+  S.shift = L.dec.shift;
+  S.mask = L.dec.mask;
+  S.bhi = L.dec.bhi;
+  S.bhiA = L.dec.bhiA;
+  S.shiftH = L.dec.shiftH;
+  S.maskH = L.dec.maskH;
+  S.n_tab_lds = L.n_tab_lds;
+  S.slice_hot = L.slice_hot.p;
+  S.lut_area = L.lut_area.p;
+  S.cls = L.cls;
   return S;
+}
+GuardDev guard_view(const Resident &L, const Solver &s) {
+  return GuardDev{s.guard_list.p, s.guard_bits.p, s.guard_tail.p, L.lut_area.p, s.guard_err.p, s.guard_visits.p, L.guard_cap(),
+                  L.guard_words()};
 }
 
 // pass B's mode for a given placement of the group vectors (glds) and n_tab slot entries in LDS; -1 = no fit
-int passB_mode(const msw_core *h, bool glds, uint32_t n_tab, bool index) {
-  const uint32_t G = h->G;
+int passB_mode(const Resident &L, bool glds, uint32_t n_tab, bool index) {
+  const uint32_t G = L.G;
   if (glds) {
     if (pass_lds_bytes(1, n_tab, G, false, index) > kLdsMax) return -1;
     // column sums at the fixed immediate distance when e_g fits below it and the image still fits
@@ -277,21 +323,21 @@ SliceClasses make_slice_classes(const uint32_t *n) {
   return C;
 }
 
-void choose_lds_mode(msw_core *h) {
+void choose_lds_mode(Resident &L) {
   const bool opts[4][2] = {{true, true}, {true, false}, {false, true}, {false, false}};
   const char *force = getenv("MSWEEP_FORCE_LDS");  // developer switch: "gt", e.g. "10" = groups in LDS, slots not
   for (auto &o : opts) {
     if (force && strlen(force) == 2 && (o[0] != (force[0] == '1') || o[1] != (force[1] == '1'))) continue;
-    const uint32_t n_tab = o[1] ? h->n_area : 0u;
-    const int gmB = passB_mode(h, o[0], n_tab, false);
+    const uint32_t n_tab = o[1] ? L.n_area : 0u;
+    const int gmB = passB_mode(L, o[0], n_tab, false);
     // (too many groups for the group vectors AND a slot table that leaves no room for the column sums: the table
     // goes to memory -- or into the hybrid area -- rather than the column sums into HBM atomics, 20 x the cost)
     if (!force && !o[0] && o[1] && gmB == 0 && !getenv("MSWEEP_GLOBAL_ATOMICS")) continue;
-    if (gmB >= 0 && pass_lds_bytes(o[0] ? 1 : 0, n_tab, h->G, true, false) <= kLdsMax) {
-      h->glds = o[0];
-      h->tlds = o[1];
-      h->gmodeB = gmB;
-      h->n_tab_lds = n_tab;
+    if (gmB >= 0 && pass_lds_bytes(o[0] ? 1 : 0, n_tab, L.G, true, false) <= kLdsMax) {
+      L.glds = o[0];
+      L.tlds = o[1];
+      L.gmodeB = gmB;
+      L.n_tab_lds = n_tab;
       return;
     }
   }
@@ -300,25 +346,25 @@ void choose_lds_mode(msw_core *h) {
 
 // LDS mode, then the record encoding that goes with it (sell.hpp): the narrowest split of a
 // 32-bit record that holds both byte offsets, else 8-byte records.  Runs before the SELL packing.
-void choose_layout(msw_core *h) {
-  choose_lds_mode(h);
-  h->enc_bhi = sell_bhi(h->n_tab_lds);
-  h->enc_bhiA = 2 * h->enc_bhi;
-  const uint64_t lo_end = 16ull * std::max<uint32_t>(h->n_area, 1);              // lo < lo_end
-  const uint64_t hi_end = (uint64_t)h->enc_bhi + 8ull * ((uint64_t)h->G + kSentinels);  // hi < hi_end
-  h->enc = kEncWide;
-  h->enc_shift = 0;
-  h->enc_mask = 0xffffffffu;
+void choose_layout(Resident &L) {
+  choose_lds_mode(L);
+  L.dec.bhi = sell_bhi(L.n_tab_lds);
+  L.dec.bhiA = 2 * L.dec.bhi;
+  const uint64_t lo_end = 16ull * std::max<uint32_t>(L.n_area, 1);              // lo < lo_end
+  const uint64_t hi_end = (uint64_t)L.dec.bhi + 8ull * ((uint64_t)L.G + kSentinels);  // hi < hi_end
+  L.enc = kEncWide;
+  L.dec.shift = 0;
+  L.dec.mask = 0xffffffffu;
   const char *force = getenv("MSWEEP_RECORD_BYTES");  // developer switch: 8 = skip the 4-byte formats
   for (uint32_t s = 5; s <= 31 && !(force && atoi(force) == 8); ++s) {
     if (lo_end <= (1ull << (s - 1)) && hi_end <= (1ull << (32 - s))) {
-      h->enc = kEncNarrow;
-      h->enc_shift = s;
-      h->enc_mask = (1u << (s - 1)) - 1u;
+      L.enc = kEncNarrow;
+      L.dec.shift = s;
+      L.dec.mask = (1u << (s - 1)) - 1u;
       break;
     }
   }
-  if (h->wide() && (hi_end > (1ull << 31) || lo_end > (1ull << 32)))
+  if (L.wide() && (hi_end > (1ull << 31) || lo_end > (1ull << 32)))
     throw Fail("likelihood too large: group / lookup-table offsets exceed the 8-byte record fields");
 }
 
@@ -326,102 +372,94 @@ void choose_layout(msw_core *h) {
 // group vectors: 4-byte records of (group, entry) INDICES when both fit 32 bits, the group vectors where
 // choose_lds_mode put them, and as many of the most-used entries in LDS as both sweeps' images leave room for.
 // Returns false (layout untouched) when it does not apply.
-bool choose_hybrid_layout(msw_core *h) {
-  if (h->tlds || h->no_hybrid) return false;
+bool choose_hybrid_layout(Resident &L, bool no_hybrid) {
+  if (L.tlds || no_hybrid) return false;
   if (const char *e = getenv("MSWEEP_HYBRID"))  // developer switch: 0 = the all-memory tables (and wide records)
     if (atoi(e) == 0) return false;
   const char *force = getenv("MSWEEP_RECORD_BYTES");
   if (force && atoi(force) == 8) return false;
   uint32_t eb = 1, gb = 1;
-  while ((1ull << eb) < std::max<uint32_t>(h->n_area, 2)) ++eb;
-  while ((1ull << gb) < (uint64_t)h->G + kSentinels) ++gb;
+  while ((1ull << eb) < std::max<uint32_t>(L.n_area, 2)) ++eb;
+  while ((1ull << gb) < (uint64_t)L.G + kSentinels) ++gb;
   if (eb + gb > 32) return false;
   // room for the table: the largest multiple of 16 entries (256 bytes) that both images hold
   uint32_t n_hot = 0;
   {
-    const int gmA = h->glds ? 1 : 0;
-    uint32_t lo = 0, hi = std::min<uint32_t>(h->n_area, (uint32_t)(kLdsMax / 16)) / 16;  // in units of 16 entries
+    const int gmA = L.glds ? 1 : 0;
+    uint32_t lo = 0, hi = std::min<uint32_t>(L.n_area, (uint32_t)(kLdsMax / 16)) / 16;  // in units of 16 entries
     while (lo < hi) {
       const uint32_t mid = (lo + hi + 1) / 2, n = mid * 16;
-      const bool ok = pass_lds_bytes(gmA, n, h->G, true, true) <= kLdsMax && passB_mode(h, h->glds, n, true) >= 0 &&
-                      (h->glds || passB_mode(h, false, n, true) == passB_mode(h, false, 0, true));
+      const bool ok = pass_lds_bytes(gmA, n, L.G, true, true) <= kLdsMax && passB_mode(L, L.glds, n, true) >= 0 &&
+                      (L.glds || passB_mode(L, false, n, true) == passB_mode(L, false, 0, true));
       if (ok) lo = mid;
       else hi = mid - 1;
     }
     n_hot = lo * 16;
   }
   if (const char *e = getenv("MSWEEP_HYBRID_HOT")) n_hot = std::min<uint32_t>(n_hot, (uint32_t)atoi(e) & ~15u);  // developer switch
-  h->enc = kEncIndex;
-  h->enc_shift = eb;
-  h->enc_mask = (1u << eb) - 1u;
-  h->n_tab_lds = std::min(n_hot, h->n_area);
+  L.enc = kEncIndex;
+  L.dec.shift = eb;
+  L.dec.mask = (1u << eb) - 1u;
+  L.n_tab_lds = std::min(n_hot, L.n_area);
   // the rows of a hot segment carry 16 * entry (entry < n_tab_lds): as many bits as the table's LDS image takes
   uint32_t hb = 4;
-  while ((1ull << hb) < 16ull * std::max<uint32_t>(h->n_tab_lds, 1)) ++hb;
+  while ((1ull << hb) < 16ull * std::max<uint32_t>(L.n_tab_lds, 1)) ++hb;
   if (hb + gb > 32) return false;  // (cannot happen while the table's image and the group vectors share 160 KB of LDS)
-  h->enc_shiftH = hb;
-  h->enc_maskH = (1u << hb) - 1u;
-  h->enc_bhi = h->enc_bhiA = sell_bhi(h->n_tab_lds);
-  h->gmodeB = passB_mode(h, h->glds, h->n_tab_lds, true);
+  L.dec.shiftH = hb;
+  L.dec.maskH = (1u << hb) - 1u;
+  L.dec.bhi = L.dec.bhiA = sell_bhi(L.n_tab_lds);
+  L.gmodeB = passB_mode(L, L.glds, L.n_tab_lds, true);
   return true;
 }
 
-void alloc_solve_state(msw_core *h) {
-  const uint32_t G = h->G, E = h->E;
-  for (DevBuf<double> *b : {&h->alpha0, &h->u, &h->os_u, &h->step_u, &h->w, &h->e, &h->N, &h->Nc,
-                            &h->Acc, &h->logth})
+// a solver's buffers for the likelihood resident in L (they only grow: a bootstrap worker gets ready by this call)
+void alloc_solve_state(const Resident &L, Solver &s) {
+  const uint32_t G = L.G, E = L.E;
+  for (DevBuf<double> *b : {&s.alpha0, &s.u, &s.os_u, &s.step_u, &s.w, &s.e, &s.N, &s.Nc,
+                            &s.Acc, &s.logth})
     b->alloc((size_t)G + kSentinels);
-  h->ew.alloc((size_t)G + kSentinels);
+  s.ew.alloc((size_t)G + kSentinels);
   // entries G.. of e / ew are the sentinel groups of SELL padding records: zero, never rewritten
-  h->e.zero(h->stream);
-  h->ew.zero(h->stream);
-  h->cvec.alloc(E);
-  h->c8.alloc((size_t)E + 64);
-  h->c8s.alloc((size_t)h->nslices * 64 + 64);  // lanes without an EC stay 0: no EC
-  h->c8s.zero(h->stream);
-  h->logc_d.alloc(E);
-  h->tabA.alloc((size_t)std::max<uint32_t>(h->n_area, 1));
-  h->tabB.alloc((size_t)std::max<uint32_t>(h->n_area, 1));
-  h->tab_built.alloc(2);
-  if (h->flavor != 0) h->lut_area.alloc(1);
-  const int nb = std::max(h->nblk, std::max(h->nblk_dense, h->npart_rows()));
-  h->partA.alloc(std::max(nb, 1024));
-  h->partS.alloc(4 * (size_t)std::max(nb, 1024));
-  h->partR.alloc(kRedfinParts * ((size_t)G / kRedfinGroups + 2));
-  h->totS.alloc(4);
-  h->commA.alloc(1);
-  h->commB.alloc(3 * (size_t)G + 4);  // column sums, two limbs of the guarded ECs' shares, ELBO terms
-  h->partAcc.alloc((size_t)std::max(nb, 1) * G);
-  h->partC.alloc(1024);
-  if (h->flavor == 0) {
-    const uint32_t nb0 = (uint32_t)std::max(h->nblk, 1);
-    // every EC a workgroup can see: its wavefronts take slices (and long ECs) round-robin, SliceStream's stride
-    static_assert(kPassThreads / 64 <= 16 && kPassThreadsB / 64 <= 16, "guard_cap / guard_bits assume <= 16 wavefronts per workgroup");
-    h->guard_cap = 64u * ((h->nslices + nb0 - 1) / nb0 + 16u) + (h->n_long + nb0 - 1) / nb0 + 16u;
-    h->guard_words = (G + 31u) / 32u;
-    h->guard_list.alloc((size_t)nb0 * h->guard_cap);
-    h->guard_bits.alloc((size_t)nb0 * 16 * h->guard_words);
-    h->guard_bits.zero(h->stream);
-    h->guard_tail.alloc(2 * (size_t)G);
-    h->guard_tail.zero(h->stream);
+  s.e.zero(s.stream);
+  s.ew.zero(s.stream);
+  s.cvec.alloc(E);
+  s.c8.alloc((size_t)E + 64);
+  s.c8s.alloc((size_t)L.nslices * 64 + 64);  // lanes without an EC stay 0: no EC
+  s.c8s.zero(s.stream);
+  s.logc_d.alloc(E);
+  s.tabA.alloc((size_t)std::max<uint32_t>(L.n_area, 1));
+  s.tabB.alloc((size_t)std::max<uint32_t>(L.n_area, 1));
+  s.tab_built.alloc(2);
+  const int nb = std::max(L.nblk, std::max(L.nblk_dense, L.npart_rows()));
+  s.partA.alloc(std::max(nb, 1024));
+  s.partS.alloc(4 * (size_t)std::max(nb, 1024));
+  s.partR.alloc(kRedfinParts * ((size_t)G / kRedfinGroups + 2));
+  s.totS.alloc(4);
+  s.commA.alloc(1);
+  s.commB.alloc(3 * (size_t)G + 4);  // column sums, two limbs of the guarded ECs' shares, ELBO terms
+  s.partAcc.alloc((size_t)std::max(nb, 1) * G);
+  s.partC.alloc(1024);
+  if (L.flavor == 0) {
+    const uint32_t nb0 = (uint32_t)std::max(L.nblk, 1);
+    s.guard_list.alloc((size_t)nb0 * L.guard_cap());
+    s.guard_bits.alloc((size_t)nb0 * 16 * L.guard_words());
+    s.guard_bits.zero(s.stream);
+    s.guard_tail.alloc(2 * (size_t)G);
+    s.guard_tail.zero(s.stream);
   }
-  if (!h->trange.p) {  // dense flavour: no tables
-    h->trange.alloc(2);
-    h->trange.zero(h->stream);
-  }
-  h->guard_err.alloc(1);
-  h->guard_err.zero(h->stream);
-  h->guard_visits.alloc(1);
-  h->guard_visits.zero(h->stream);
-  h->sc.alloc(1);
-  h->tr_bound.alloc(kMaxTrace);
-  h->tr_newnorm.alloc(kMaxTrace);
-  h->tr_beta.alloc(kMaxTrace);
-  h->tr_reset.alloc(kMaxTrace);
-  if (!h->sc_host) MSW_HIP(hipHostMalloc((void **)&h->sc_host, sizeof(Scalars)));
-  if (!h->ev0) {
-    MSW_HIP(hipEventCreate(&h->ev0));
-    MSW_HIP(hipEventCreate(&h->ev1));
+  s.guard_err.alloc(1);
+  s.guard_err.zero(s.stream);
+  s.guard_visits.alloc(1);
+  s.guard_visits.zero(s.stream);
+  s.sc.alloc(1);
+  s.tr_bound.alloc(kMaxTrace);
+  s.tr_newnorm.alloc(kMaxTrace);
+  s.tr_beta.alloc(kMaxTrace);
+  s.tr_reset.alloc(kMaxTrace);
+  if (!s.sc_host) MSW_HIP(hipHostMalloc((void **)&s.sc_host, sizeof(Scalars)));
+  if (!s.ev0) {
+    MSW_HIP(hipEventCreate(&s.ev0));
+    MSW_HIP(hipEventCreate(&s.ev1));
   }
 }
 
@@ -439,50 +477,50 @@ void prepare_sweep(K k, size_t lds, size_t &lds_set) {
   }
 }
 template <int ENC, bool GL, bool TL>
-void launch_passA_t(msw_core *h) {
-  const size_t lds = pass_lds_bytes(GL ? 1 : 0, h->n_tab_lds, h->G, true, ENC == kEncIndex);
+void launch_passA_t(const Resident &L, Solver &s) {
+  const size_t lds = pass_lds_bytes(GL ? 1 : 0, L.n_tab_lds, L.G, true, ENC == kEncIndex);
   // ML: some slices hold ECs over several lanes (sell.hpp slice classes) -- an instantiation of its own: the few
   // scalar operations and branches the classes cost per slice are 2-3 % of a sweep over short slices (cfg3, cfg5)
-  const bool ml = h->cls.s0[kSliceClasses - 1] > 0;
+  const bool ml = L.cls.s0[kSliceClasses - 1] > 0;
   auto k = ml ? k_passA<ENC, GL, TL, true> : k_passA<ENC, GL, TL, false>;
-  prepare_sweep(k, lds, h->lds_attr[0][(ml ? 40 : 0) + ENC * 4 + (GL ? 2 : 0) + (TL ? 1 : 0)]);
-  hipLaunchKernelGGL(k, dim3(h->nblk), dim3(pass_threads_A<ENC>()), lds, h->stream, h->sc.p, sell_view(h),
-                     h->ew.p, h->tabA.p, h->partA.p, h->partR.p, (int)((h->G + kRedfinGroups - 1) / kRedfinGroups),
-                     h->guard_view());
+  prepare_sweep(k, lds, s.lds_attr[0][(ml ? 40 : 0) + ENC * 4 + (GL ? 2 : 0) + (TL ? 1 : 0)]);
+  hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_A<ENC>()), lds, s.stream, s.sc.p, sell_view(L, s),
+                     s.ew.p, s.tabA.p, s.partA.p, s.partR.p, (int)((L.G + kRedfinGroups - 1) / kRedfinGroups),
+                     guard_view(L, s));
 }
 template <int ENC, int GM, bool TL>
-void launch_passB_t(msw_core *h) {
-  const size_t lds = pass_lds_bytes(GM, h->n_tab_lds, h->G, false, ENC == kEncIndex);
-  const bool ml = h->cls.s0[kSliceClasses - 1] > 0;
+void launch_passB_t(const Resident &L, Solver &s) {
+  const size_t lds = pass_lds_bytes(GM, L.n_tab_lds, L.G, false, ENC == kEncIndex);
+  const bool ml = L.cls.s0[kSliceClasses - 1] > 0;
   if constexpr (ENC == kEncNarrow) {
-    if (h->passB_rc8 && !ml) {  // (nearly) every slice at most 8 rows: 16 wavefronts per workgroup (finish_sell)
+    if (L.passB_rc8 && !ml) {  // (nearly) every slice at most 8 rows: 16 wavefronts per workgroup (finish_sell)
       auto k8 = k_passB<ENC, GM, TL, false, 8>;
-      prepare_sweep(k8, lds, h->lds_attr[2][2 * GM + (TL ? 1 : 0)]);
+      prepare_sweep(k8, lds, s.lds_attr[2][2 * GM + (TL ? 1 : 0)]);
       const auto rg_of = [&](uint32_t g0) {
-        return GM == 4 ? RangeB{g0, std::min<uint32_t>(kRangeGroups, h->G - g0), g0 == 0 ? 1 : 0} : RangeB{0, 0, 1};
+        return GM == 4 ? RangeB{g0, std::min<uint32_t>(kRangeGroups, L.G - g0), g0 == 0 ? 1 : 0} : RangeB{0, 0, 1};
       };
-      for (uint32_t g0 = 0; g0 < (GM == 4 ? h->G : 1u); g0 += kRangeGroups)
-        hipLaunchKernelGGL(k8, dim3(h->nblk), dim3(pass_threads_B<ENC, 8>()), lds, h->stream, h->sc.p, sell_view(h), h->e.p,
-                           h->tabB.p, h->partAcc.p, h->partS.p, h->Acc.p, rg_of(g0), h->guard_view());
+      for (uint32_t g0 = 0; g0 < (GM == 4 ? L.G : 1u); g0 += kRangeGroups)
+        hipLaunchKernelGGL(k8, dim3(L.nblk), dim3(pass_threads_B<ENC, 8>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+                           s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p, rg_of(g0), guard_view(L, s));
       return;
     }
   }
   auto k = ml ? k_passB<ENC, GM, TL, true> : k_passB<ENC, GM, TL, false>;
-  prepare_sweep(k, lds, h->lds_attr[1][(ml ? 40 : 0) + ENC * 10 + 2 * GM + (TL ? 1 : 0)]);
+  prepare_sweep(k, lds, s.lds_attr[1][(ml ? 40 : 0) + ENC * 10 + 2 * GM + (TL ? 1 : 0)]);
   if (GM == 4) {  // one run per range of groups; the first also delivers the ELBO terms
-    for (uint32_t g0 = 0; g0 < h->G; g0 += kRangeGroups)
-      hipLaunchKernelGGL(k, dim3(h->nblk), dim3(pass_threads_B<ENC>()), lds, h->stream, h->sc.p, sell_view(h), h->e.p,
-                         h->tabB.p, h->partAcc.p, h->partS.p, h->Acc.p,
-                         RangeB{g0, std::min<uint32_t>(kRangeGroups, h->G - g0), g0 == 0 ? 1 : 0}, h->guard_view());
+    for (uint32_t g0 = 0; g0 < L.G; g0 += kRangeGroups)
+      hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+                         s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p,
+                         RangeB{g0, std::min<uint32_t>(kRangeGroups, L.G - g0), g0 == 0 ? 1 : 0}, guard_view(L, s));
     return;
   }
-  hipLaunchKernelGGL(k, dim3(h->nblk), dim3(pass_threads_B<ENC>()), lds, h->stream, h->sc.p, sell_view(h), h->e.p,
-                     h->tabB.p, h->partAcc.p, h->partS.p, h->Acc.p, RangeB{0, 0, 1}, h->guard_view());
+  hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+                     s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p, RangeB{0, 0, 1}, guard_view(L, s));
 }
 
 #define MSW_DISPATCH3(fn, ...)                                                       \
   do {                                                                               \
-    const int key = h->enc * 4 + (h->glds ? 2 : 0) + (h->tlds ? 1 : 0);              \
+    const int key = L.enc * 4 + (L.glds ? 2 : 0) + (L.tlds ? 1 : 0);              \
     switch (key) {                                                                   \
       case 0: fn<kEncNarrow, false, false>(__VA_ARGS__); break;                      \
       case 1: fn<kEncNarrow, false, true>(__VA_ARGS__); break;                       \
@@ -501,7 +539,7 @@ void launch_passB_t(msw_core *h) {
   } while (0)
 #define MSW_DISPATCH_B(fn, ...)                                                      \
   do {                                                                               \
-    const int key = h->enc * 10 + 2 * h->gmodeB + (h->tlds ? 1 : 0);                 \
+    const int key = L.enc * 10 + 2 * L.gmodeB + (L.tlds ? 1 : 0);                 \
     switch (key) {                                                                   \
       case 0: fn<kEncNarrow, 0, false>(__VA_ARGS__); break;                          \
       case 1: fn<kEncNarrow, 0, true>(__VA_ARGS__); break;                           \
@@ -538,29 +576,29 @@ void launch_passB_t(msw_core *h) {
   } while (0)
 
 template <int NREG>
-void launch_dense_A(msw_core *h) {
-  hipLaunchKernelGGL(k_dense_passA<NREG>, dim3(h->nblk_dense), dim3(256), 0, h->stream, h->sc.p,
-                     h->Lt.p, (int)h->G, h->E, h->u.p, h->w.p, h->partA.p);
+void launch_dense_A(const Resident &L, Solver &s) {
+  hipLaunchKernelGGL(k_dense_passA<NREG>, dim3(L.nblk_dense), dim3(256), 0, s.stream, s.sc.p,
+                     L.Lt.p, (int)L.G, L.E, s.u.p, s.w.p, s.partA.p);
 }
 template <int NREG>
-void launch_dense_B(msw_core *h) {
-  const size_t lds = (32 + 4 * (size_t)h->G) * sizeof(double);
-  hipLaunchKernelGGL(k_dense_passB<NREG>, dim3(h->nblk_dense), dim3(256), lds, h->stream, h->sc.p,
-                     h->Lt.p, (int)h->G, h->E, h->cvec.p, h->u.p, h->partAcc.p, h->partS.p);
+void launch_dense_B(const Resident &L, Solver &s) {
+  const size_t lds = (32 + 4 * (size_t)L.G) * sizeof(double);
+  hipLaunchKernelGGL(k_dense_passB<NREG>, dim3(L.nblk_dense), dim3(256), lds, s.stream, s.sc.p,
+                     L.Lt.p, (int)L.G, L.E, s.cvec.p, s.u.p, s.partAcc.p, s.partS.p);
 }
 template <int NREG>
-void launch_dense_big_A(msw_core *h) {
-  hipLaunchKernelGGL(k_dense_big_passA<NREG>, dim3(h->nblk_dense), dim3(256), 0, h->stream, h->sc.p,
-                     h->Lt.p, (int)h->G, h->E, h->u.p, h->w.p, h->partA.p);
+void launch_dense_big_A(const Resident &L, Solver &s) {
+  hipLaunchKernelGGL(k_dense_big_passA<NREG>, dim3(L.nblk_dense), dim3(256), 0, s.stream, s.sc.p,
+                     L.Lt.p, (int)L.G, L.E, s.u.p, s.w.p, s.partA.p);
 }
 template <int NREG>
-void launch_dense_big_B(msw_core *h) {
-  hipLaunchKernelGGL(k_dense_big_passB<NREG>, dim3(h->nblk_dense), dim3(256), 0, h->stream, h->sc.p,
-                     h->Lt.p, (int)h->G, h->E, h->cvec.p, h->u.p, h->partAcc.p, h->partS.p);
+void launch_dense_big_B(const Resident &L, Solver &s) {
+  hipLaunchKernelGGL(k_dense_big_passB<NREG>, dim3(L.nblk_dense), dim3(256), 0, s.stream, s.sc.p,
+                     L.Lt.p, (int)L.G, L.E, s.cvec.p, s.u.p, s.partAcc.p, s.partS.p);
 }
 #define MSW_DISPATCH_NREG(fn, fnbig, ...)                \
   do {                                                   \
-    switch (h->nreg) {                                   \
+    switch (L.nreg) {                                   \
       case 1: fn<1>(__VA_ARGS__); break;                 \
       case 2: fn<2>(__VA_ARGS__); break;                 \
       case 4: fn<4>(__VA_ARGS__); break;                 \
@@ -572,196 +610,196 @@ void launch_dense_big_B(msw_core *h) {
     }                                                    \
   } while (0)
 
-void launch_passA(msw_core *h) {
+void launch_passA(const Resident &L, Solver &s) {
   std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-  if (h->profiling) {
-    ev = &next_pair(h->evA, h->evA_used);
-    MSW_HIP(hipEventRecord(ev->first, h->stream));
+  if (s.profiling) {
+    ev = &next_pair(s.evA, s.evA_used);
+    MSW_HIP(hipEventRecord(ev->first, s.stream));
   }
-  if (h->flavor == 0) MSW_DISPATCH3(launch_passA_t, h);
-  else MSW_DISPATCH_NREG(launch_dense_A, launch_dense_big_A, h);
+  if (L.flavor == 0) MSW_DISPATCH3(launch_passA_t, L, s);
+  else MSW_DISPATCH_NREG(launch_dense_A, launch_dense_big_A, L, s);
   MSW_HIP(hipGetLastError());
-  if (ev) MSW_HIP(hipEventRecord(ev->second, h->stream));
-  h->timing.passA_launches++;
+  if (ev) MSW_HIP(hipEventRecord(ev->second, s.stream));
+  s.timing.passA_launches++;
 }
 
 // --emprecision float: the fp32 sweep of em_f32_kernels.hpp (run_em decides; one persistent workgroup per CU)
-bool em_f32_layout_ok(const msw_core *h) {
-  return kFx && h->flavor == 0 && h->enc == kEncNarrow && h->glds && h->tlds && !h->comm && h->n_tab_lds == h->n_area &&
-         h->G <= (uint32_t)(kStepRegs * 1024) && em_f32_lds_bytes(h->n_tab_lds, h->G) <= kLdsMax &&
+bool em_f32_layout_ok(const Resident &L, const Solver &s) {
+  return kFx && L.flavor == 0 && L.enc == kEncNarrow && L.glds && L.tlds && !s.comm() && L.n_tab_lds == L.n_area &&
+         L.G <= (uint32_t)(kStepRegs * 1024) && em_f32_lds_bytes(L.n_tab_lds, L.G) <= kLdsMax &&
          !getenv("MSWEEP_EM_FLOAT_AS_DOUBLE");  // (developer switch: the fp64 kernels under MSW_PREC_FLOAT, as until round 4)
 }
-void launch_em_passB_f32(msw_core *h) {
-  const size_t lds = em_f32_lds_bytes(h->n_tab_lds, h->G);
-  const bool ml = h->cls.s0[kSliceClasses - 1] > 0;
+void launch_em_passB_f32(const Resident &L, Solver &s) {
+  const size_t lds = em_f32_lds_bytes(L.n_tab_lds, L.G);
+  const bool ml = L.cls.s0[kSliceClasses - 1] > 0;
   auto k = ml ? k_em_passB_f32<true> : k_em_passB_f32<false>;
-  prepare_sweep(k, lds, h->lds_attr[2][30 + (ml ? 1 : 0)]);
-  hipLaunchKernelGGL(k, dim3(h->nblk), dim3(1024), lds, h->stream, h->sc.p, sell_view(h), h->e.p, h->e32.p, h->tab32.p,
-                     h->partAcc.p, h->partS.p, h->guard_view());
+  prepare_sweep(k, lds, s.lds_attr[2][30 + (ml ? 1 : 0)]);
+  hipLaunchKernelGGL(k, dim3(L.nblk), dim3(1024), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p, s.e32.p, s.tab32.p,
+                     s.partAcc.p, s.partS.p, guard_view(L, s));
 }
 
-void launch_passB(msw_core *h) {
+void launch_passB(const Resident &L, Solver &s) {
   std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-  if (h->profiling) {
-    ev = &next_pair(h->evB, h->evB_used);
-    MSW_HIP(hipEventRecord(ev->first, h->stream));
+  if (s.profiling) {
+    ev = &next_pair(s.evB, s.evB_used);
+    MSW_HIP(hipEventRecord(ev->first, s.stream));
   }
-  if (h->flavor == 0 && h->em_f32) {
-    launch_em_passB_f32(h);
-  } else if (h->flavor == 0) {
-    if (h->gmodeB == 0) MSW_HIP(hipMemsetAsync(h->Acc.p, 0, ((size_t)h->G + kSentinels) * sizeof(double), h->stream));
-    MSW_DISPATCH_B(launch_passB_t, h);
+  if (L.flavor == 0 && s.em_f32) {
+    launch_em_passB_f32(L, s);
+  } else if (L.flavor == 0) {
+    if (L.gmodeB == 0) MSW_HIP(hipMemsetAsync(s.Acc.p, 0, ((size_t)L.G + kSentinels) * sizeof(double), s.stream));
+    MSW_DISPATCH_B(launch_passB_t, L, s);
   } else {
-    MSW_DISPATCH_NREG(launch_dense_B, launch_dense_big_B, h);
+    MSW_DISPATCH_NREG(launch_dense_B, launch_dense_big_B, L, s);
   }
   MSW_HIP(hipGetLastError());
-  if (ev) MSW_HIP(hipEventRecord(ev->second, h->stream));
-  h->timing.passB_launches++;
+  if (ev) MSW_HIP(hipEventRecord(ev->second, s.stream));
+  s.timing.passB_launches++;
   // column sums across workgroups + N_g / lgamma / digamma, spread over G/16 workgroups
-  const bool partials = (h->flavor == 1) || h->gmodeB > 0 || h->em_f32;
-  const int nb = h->npart_rows();
+  const bool partials = (L.flavor == 1) || L.gmodeB > 0 || s.em_f32;
+  const int nb = L.npart_rows();
   // the CSR sweeps leave fixed-point integer rows (kFx); 2: the fp32 EM sweep's, without the per-group factor
-  const int fxrows = h->flavor == 0 ? (h->em_f32 ? 2 : 1) : 0;
-  if (h->comm) {
+  const int fxrows = L.flavor == 0 ? (s.em_f32 ? 2 : 1) : 0;
+  if (s.comm()) {
     // EC-sharded: local column sums + ELBO terms -> one all-reduce -> k_redfin on the totals.  The
     // fixed-point column sums are all-reduced as INTEGERS: exact, so the totals -- and with them every
     // N_g -- are the same bits whatever the number of ranks the ECs are spread over.
-    const size_t G3 = 3 * (size_t)h->G;
+    const size_t G3 = 3 * (size_t)L.G;
     std::pair<hipEvent_t, hipEvent_t> *evc = nullptr;
-    if (h->profiling) {
-      evc = &next_pair(h->evC, h->evC_used);
-      MSW_HIP(hipEventRecord(evc->first, h->stream));
+    if (s.profiling) {
+      evc = &next_pair(s.evC, s.evC_used);
+      MSW_HIP(hipEventRecord(evc->first, s.stream));
     }
-    hipLaunchKernelGGL(k_colsum, dim3((h->G + 63) / 64), dim3(1024), 0, h->stream, h->sc.p, (int)h->G,
-                       partials ? nb : 0, fxrows, nb, h->partAcc.p, h->Acc.p, h->partS.p,
-                       fxrows ? h->guard_tail.p : nullptr, h->commB.p);
+    hipLaunchKernelGGL(k_colsum, dim3((L.G + 63) / 64), dim3(1024), 0, s.stream, s.sc.p, (int)L.G,
+                       partials ? nb : 0, fxrows, nb, s.partAcc.p, s.Acc.p, s.partS.p,
+                       fxrows ? s.guard_tail.p : nullptr, s.commB.p);
     if (kFx && fxrows) {
-      h->comm->allreduce_mixed(reinterpret_cast<uint64_t *>(h->commB.p), G3, h->commB.p + G3, 4, h->stream);
+      s.comm()->allreduce_mixed(reinterpret_cast<uint64_t *>(s.commB.p), G3, s.commB.p + G3, 4, s.stream);
     } else {  // fp64 column sums (dense flavour, MSW_FX=0 builds): doubles, then the integer limbs
-      h->comm->allreduce(h->commB.p, (size_t)h->G, h->stream);
-      h->comm->allreduce_mixed(reinterpret_cast<uint64_t *>(h->commB.p) + h->G, 2 * (size_t)h->G, h->commB.p + G3, 4,
-                               h->stream);
+      s.comm()->allreduce(s.commB.p, (size_t)L.G, s.stream);
+      s.comm()->allreduce_mixed(reinterpret_cast<uint64_t *>(s.commB.p) + L.G, 2 * (size_t)L.G, s.commB.p + G3, 4,
+                               s.stream);
     }
-    if (evc) MSW_HIP(hipEventRecord(evc->second, h->stream));
-    hipLaunchKernelGGL(k_redfin, dim3((h->G + kRedfinGroups - 1) / kRedfinGroups), dim3(kRedfinThreads), 0, h->stream,
-                       h->sc.p, (int)h->G, 0, fxrows, reinterpret_cast<unsigned long long *>(h->commB.p) + h->G, 0, 1,
-                       h->partAcc.p, h->commB.p, h->commB.p + G3, h->e.p, h->u.p,
-                       h->alpha0.p, h->Nc.p, h->N.p, h->w.p, h->ew.p, h->partR.p, h->totS.p);
+    if (evc) MSW_HIP(hipEventRecord(evc->second, s.stream));
+    hipLaunchKernelGGL(k_redfin, dim3((L.G + kRedfinGroups - 1) / kRedfinGroups), dim3(kRedfinThreads), 0, s.stream,
+                       s.sc.p, (int)L.G, 0, fxrows, reinterpret_cast<unsigned long long *>(s.commB.p) + L.G, 0, 1,
+                       s.partAcc.p, s.commB.p, s.commB.p + G3, s.e.p, s.u.p,
+                       s.alpha0.p, s.Nc.p, s.N.p, s.w.p, s.ew.p, s.partR.p, s.totS.p);
     return;
   }
-  hipLaunchKernelGGL(k_redfin, dim3((h->G + kRedfinGroups - 1) / kRedfinGroups), dim3(kRedfinThreads), 0, h->stream,
-                     h->sc.p, (int)h->G, partials ? nb : 0, fxrows, fxrows ? h->guard_tail.p : nullptr, 1, nb,
-                     h->partAcc.p, h->Acc.p, h->partS.p, h->e.p,
-                     h->u.p, h->alpha0.p, h->Nc.p, h->N.p, h->w.p, h->ew.p, h->partR.p, h->totS.p);
+  hipLaunchKernelGGL(k_redfin, dim3((L.G + kRedfinGroups - 1) / kRedfinGroups), dim3(kRedfinThreads), 0, s.stream,
+                     s.sc.p, (int)L.G, partials ? nb : 0, fxrows, fxrows ? s.guard_tail.p : nullptr, 1, nb,
+                     s.partAcc.p, s.Acc.p, s.partS.p, s.e.p,
+                     s.u.p, s.alpha0.p, s.Nc.p, s.N.p, s.w.p, s.ew.p, s.partR.p, s.totS.p);
 }
 
 // partS as seen by k_fin / k_em_fin: the all-reduced totals when sharded
-const double *fin_partS(msw_core *h) { return h->comm ? h->commB.p + 3 * (size_t)h->G : h->partS.p; }
-int fin_npartS(msw_core *h) { return h->comm ? 1 : h->npart_rows(); }
+const double *fin_partS(const Resident &L, Solver &s) { return s.comm() ? s.commB.p + 3 * (size_t)L.G : s.partS.p; }
+int fin_npartS(const Resident &L, Solver &s) { return s.comm() ? 1 : L.npart_rows(); }
 
 // slot areas beyond kTabInline entries: the tables are rebuilt by their own kernel after every
 // kernel that may have moved a (it returns at once when they are current)
-void launch_tables(msw_core *h) {
-  if (h->flavor != 0 || h->n_area <= (uint32_t)kTabInline) return;
-  const unsigned nb = std::min<unsigned>((h->n_area + 255) / 256, (unsigned)h->n_cu * 8);
-  hipLaunchKernelGGL(k_tables, dim3(nb), dim3(256), 0, h->stream, h->sc.p, (int)h->n_area, h->lut_area.p, h->tabs(),
-                     h->tab_built.p);
+void launch_tables(const Resident &L, Solver &s) {
+  if (L.flavor != 0 || L.n_area <= (uint32_t)kTabInline) return;
+  const unsigned nb = std::min<unsigned>((L.n_area + 255) / 256, (unsigned)s.n_cu * 8);
+  hipLaunchKernelGGL(k_tables, dim3(nb), dim3(256), 0, s.stream, s.sc.p, (int)L.n_area, L.lut_area.p, s.tabs(),
+                     s.tab_built.p);
 }
 
 // the verdict on the pending evaluation + the next step (state_kernels.hpp k_finstep); mode 1: the verdict alone
-void launch_finstep(msw_core *h, int mode) {
-  TraceDev tr{h->tr_bound.p, h->tr_newnorm.p, h->tr_beta.p, h->tr_theta.p, h->tr_reset.p};
-  const double *pA = h->partA.p;
-  int npA = h->flavor == 0 ? h->nblk : h->nblk_dense;
-  if (h->comm) {  // |g|^2 summed over the EC shards (run_rcg)
-    pA = h->commA.p;
+void launch_finstep(const Resident &L, Solver &s, int mode) {
+  TraceDev tr{s.tr_bound.p, s.tr_newnorm.p, s.tr_beta.p, s.tr_theta.p, s.tr_reset.p};
+  const double *pA = s.partA.p;
+  int npA = L.flavor == 0 ? L.nblk : L.nblk_dense;
+  if (s.comm()) {  // |g|^2 summed over the EC shards (run_rcg)
+    pA = s.commA.p;
     npA = 1;
   }
-  hipLaunchKernelGGL(k_finstep, dim3(1), dim3(1024), 0, h->stream, h->sc.p, mode, (int)h->G, h->n_tab_inline(), npA, pA,
-                     (int)((h->G + kRedfinGroups - 1) / kRedfinGroups), h->totS.p, h->partR.p, h->Nc.p, h->w.p, h->u.p,
-                     h->os_u.p, h->step_u.p, h->lut_area.p, h->e.p, h->tabs(), tr);
-  launch_tables(h);
+  hipLaunchKernelGGL(k_finstep, dim3(1), dim3(1024), 0, s.stream, s.sc.p, mode, (int)L.G, L.n_tab_inline(), npA, pA,
+                     (int)((L.G + kRedfinGroups - 1) / kRedfinGroups), s.totS.p, s.partR.p, s.Nc.p, s.w.p, s.u.p,
+                     s.os_u.p, s.step_u.p, L.lut_area.p, s.e.p, s.tabs(), tr);
+  launch_tables(L, s);
 }
 
-void poll(msw_core *h) {
-  MSW_HIP(hipMemcpyAsync(h->sc_host, h->sc.p, sizeof(Scalars), hipMemcpyDeviceToHost, h->stream));
-  MSW_HIP(hipStreamSynchronize(h->stream));
-  if (h->comm) h->comm->check();
+void poll(Solver &s) {
+  MSW_HIP(hipMemcpyAsync(s.sc_host, s.sc.p, sizeof(Scalars), hipMemcpyDeviceToHost, s.stream));
+  MSW_HIP(hipStreamSynchronize(s.stream));
+  if (s.comm()) s.comm()->check();
 }
 
 // Inputs of one solve: c_j (from log counts or from bootstrap counts already on the device) and
 // the prior.  Leaves per-block partial sums of c in partC for k_init_state.
 constexpr int kCvecBlocks = 512;
-void prepare_inputs(msw_core *h, const double *logc_host, const uint32_t *counts_dev,
+void prepare_inputs(const Resident &L, Solver &s, const double *logc_host, const uint32_t *counts_dev,
                     const double *alpha0_host) {
-  if (h->flavor < 0) throw Fail("no likelihood resident: call msw_core_set_csr / set_dense_logl first");
-  const uint32_t E = h->E, G = h->G;
+  if (L.flavor < 0) throw Fail("no likelihood resident: call msw_core_set_csr / set_dense_logl first");
+  const uint32_t E = L.E, G = L.G;
   if (counts_dev) {
-    hipLaunchKernelGGL(k_cvec_from_counts, dim3(kCvecBlocks), dim3(256), 0, h->stream, counts_dev,
-                       h->flavor == 0 ? h->perm.p : nullptr, E, h->cvec.p, h->c8.p, h->partC.p, h->cls, h->n_long,
-                       h->flavor == 0 ? h->c8s.p : nullptr);
+    hipLaunchKernelGGL(k_cvec_from_counts, dim3(kCvecBlocks), dim3(256), 0, s.stream, counts_dev,
+                       L.flavor == 0 ? L.perm.p : nullptr, E, s.cvec.p, s.c8.p, s.partC.p, L.cls, L.n_long,
+                       L.flavor == 0 ? s.c8s.p : nullptr);
   } else {
-    const double *src = h->logc_d.p;
+    const double *src = s.logc_d.p;
     if (logc_host) {
-      MSW_HIP(hipMemcpyAsync(h->logc_d.p, logc_host, E * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      MSW_HIP(hipMemcpyAsync(s.logc_d.p, logc_host, E * sizeof(double), hipMemcpyHostToDevice, s.stream));
     } else {  // the log counts msw_core_build_likelihood left on the device: no 8 * E byte upload
-      if (!h->have_logc_res) throw Fail("null logc: only a likelihood built by msw_core_build_likelihood keeps its log counts");
-      src = h->logc_res.p;
+      if (!L.have_logc_res) throw Fail("null logc: only a likelihood built by msw_core_build_likelihood keeps its log counts");
+      src = L.logc_res.p;
     }
-    hipLaunchKernelGGL(k_cvec_from_logc, dim3(kCvecBlocks), dim3(256), 0, h->stream, src,
-                       h->flavor == 0 ? h->perm.p : nullptr, E, h->cvec.p, h->c8.p, h->partC.p, h->cls, h->n_long,
-                       h->flavor == 0 ? h->c8s.p : nullptr);
+    hipLaunchKernelGGL(k_cvec_from_logc, dim3(kCvecBlocks), dim3(256), 0, s.stream, src,
+                       L.flavor == 0 ? L.perm.p : nullptr, E, s.cvec.p, s.c8.p, s.partC.p, L.cls, L.n_long,
+                       L.flavor == 0 ? s.c8s.p : nullptr);
   }
   if (alpha0_host)
-    MSW_HIP(hipMemcpyAsync(h->alpha0.p, alpha0_host, G * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    MSW_HIP(hipMemcpyAsync(s.alpha0.p, alpha0_host, G * sizeof(double), hipMemcpyHostToDevice, s.stream));
   MSW_HIP(hipGetLastError());
   // logc_host / alpha0_host may be pageable caller memory: finish the copies before returning
-  MSW_HIP(hipStreamSynchronize(h->stream));
-  h->prepared = true;
+  MSW_HIP(hipStreamSynchronize(s.stream));
+  s.prepared = true;
 }
 
 // argument / state errors of a solve: thrown BEFORE anything that a peer of a sharded solve could wait for
-void validate_solve(const msw_core *, size_t max_iters, int algo, int prec) {
+void validate_solve(size_t max_iters, int algo, int prec) {
   if (algo != MSW_ALGO_RCG && algo != MSW_ALGO_EM) throw Fail("unknown algorithm id");
   if (prec != MSW_PREC_DOUBLE && prec != MSW_PREC_FLOAT) throw Fail("unknown precision id");
   if (max_iters == 0 || max_iters > (size_t)std::numeric_limits<int32_t>::max())
     throw Fail("max_iters out of range");
 }
 
-void begin_solve(msw_core *h, double tol, size_t max_iters) {
-  const uint32_t G = h->G;
-  if (h->trace_theta) h->tr_theta.alloc(h->trace_theta * G);
-  const double *cpart = h->partC.p;
+void begin_solve(const Resident &L, Solver &s, double tol, size_t max_iters) {
+  const uint32_t G = L.G;
+  if (s.trace_theta) s.tr_theta.alloc(s.trace_theta * G);
+  const double *cpart = s.partC.p;
   int ncpart = kCvecBlocks;
-  if (h->comm) {  // global sum of the EC counts (bound constant, theta normalisation)
-    h->comm->rendezvous();  // the ranks' calls may be seconds apart on the host: meet before the device-side waits
-    hipLaunchKernelGGL(k_sum_scalar, dim3(1), dim3(1024), 0, h->stream, h->sc.p, 0, kCvecBlocks, h->partC.p,
-                       h->commA.p);
-    h->comm->allreduce(h->commA.p, 1, h->stream);
-    cpart = h->commA.p;
+  if (s.comm()) {  // global sum of the EC counts (bound constant, theta normalisation)
+    s.comm()->rendezvous();  // the ranks' calls may be seconds apart on the host: meet before the device-side waits
+    hipLaunchKernelGGL(k_sum_scalar, dim3(1), dim3(1024), 0, s.stream, s.sc.p, 0, kCvecBlocks, s.partC.p,
+                       s.commA.p);
+    s.comm()->allreduce(s.commA.p, 1, s.stream);
+    cpart = s.commA.p;
     ncpart = 1;
   }
-  hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1024), 0, h->stream, h->sc.p, (int)G, ncpart,
-                     cpart, h->alpha0.p, h->u.p, h->os_u.p, h->step_u.p, tol, (int)max_iters,
-                     h->fixed_iters ? 1 : 0, (int)h->trace_theta, h->flavor, h->logzi, h->opts, h->tab_built.p,
-                     h->trange.p);
+  hipLaunchKernelGGL(k_init_state, dim3(1), dim3(1024), 0, s.stream, s.sc.p, (int)G, ncpart,
+                     cpart, s.alpha0.p, s.u.p, s.os_u.p, s.step_u.p, tol, (int)max_iters,
+                     s.fixed_iters ? 1 : 0, (int)s.trace_theta, L.flavor, L.logzi, s.opts, s.tab_built.p,
+                     L.trange.p);
   MSW_HIP(hipGetLastError());
 }
 
 // iters_start > 0: the solve on the handle is continued (msw_core_continue) -- no initial evaluation
-void run_rcg(msw_core *h, size_t max_iters, size_t iters_start = 0) {
-  const int G = (int)h->G, n_lut = h->n_tab_inline();
-  if (iters_start > 0 && h->comm) h->comm->rendezvous();  // msw_core_continue: as begin_solve
+void run_rcg(const Resident &L, Solver &s, size_t max_iters, size_t iters_start = 0) {
+  const int G = (int)L.G, n_lut = L.n_tab_inline();
+  if (iters_start > 0 && s.comm()) s.comm()->rendezvous();  // msw_core_continue: as begin_solve
   if (iters_start == 0) {
     // initial update_N_k on gamma = log(1/G): the first slot's k_finstep finds it as Scalars::have_eval = 2
-    hipLaunchKernelGGL(k_prepB, dim3(1), dim3(1024), 0, h->stream, h->sc.p, G, n_lut, h->u.p, h->lut_area.p,
-                       h->e.p, h->tabs());
-    launch_tables(h);
-    launch_passB(h);
-    h->timing.passB_launches--;  // the initial evaluation is not an iteration
-    if (h->profiling && h->evB_used) h->evB_used--;
+    hipLaunchKernelGGL(k_prepB, dim3(1), dim3(1024), 0, s.stream, s.sc.p, G, n_lut, s.u.p, L.lut_area.p,
+                       s.e.p, s.tabs());
+    launch_tables(L, s);
+    launch_passB(L, s);
+    s.timing.passB_launches--;  // the initial evaluation is not an iteration
+    if (s.profiling && s.evB_used) s.evB_used--;
   }
-  const int nbA = h->flavor == 0 ? h->nblk : h->nblk_dense;
+  const int nbA = L.flavor == 0 ? L.nblk : L.nblk_dense;
   // Slots (state_kernels.hpp k_finstep): k_passA -> k_finstep -> k_passB (+ k_redfin); one per iteration plus one per
   // rejected step.  The verdict on a slot's evaluation is taken by the NEXT slot's k_finstep, so the iteration count
   // the host polls lags the evaluations by one: enqueue as many slots as iterations are still missing, poll, repeat;
@@ -771,141 +809,141 @@ void run_rcg(msw_core *h, size_t max_iters, size_t iters_start = 0) {
   for (;;) {
     // fixed-iteration runs know how many slots are missing; otherwise poll every kIterBatch
     const size_t missing = std::max<size_t>(1, max_iters - std::min(max_iters, iters_done));
-    const size_t batch = h->fixed_iters ? std::min<size_t>(256, missing) : std::min<size_t>(kIterBatch, missing);
+    const size_t batch = s.fixed_iters ? std::min<size_t>(256, missing) : std::min<size_t>(kIterBatch, missing);
     for (size_t b = 0; b < batch; ++b) {
-      launch_passA(h);
-      if (h->comm) {  // |g|^2 summed over the EC shards
+      launch_passA(L, s);
+      if (s.comm()) {  // |g|^2 summed over the EC shards
         std::pair<hipEvent_t, hipEvent_t> *evc = nullptr;
-        if (h->profiling) {
-          evc = &next_pair(h->evC, h->evC_used);
-          MSW_HIP(hipEventRecord(evc->first, h->stream));
+        if (s.profiling) {
+          evc = &next_pair(s.evC, s.evC_used);
+          MSW_HIP(hipEventRecord(evc->first, s.stream));
         }
-        hipLaunchKernelGGL(k_sum_scalar, dim3(1), dim3(1024), 0, h->stream, h->sc.p, 1, nbA, h->partA.p,
-                           h->commA.p);
-        h->comm->allreduce(h->commA.p, 1, h->stream);
-        if (evc) MSW_HIP(hipEventRecord(evc->second, h->stream));
+        hipLaunchKernelGGL(k_sum_scalar, dim3(1), dim3(1024), 0, s.stream, s.sc.p, 1, nbA, s.partA.p,
+                           s.commA.p);
+        s.comm()->allreduce(s.commA.p, 1, s.stream);
+        if (evc) MSW_HIP(hipEventRecord(evc->second, s.stream));
       }
-      launch_finstep(h, 0);
-      launch_passB(h);
+      launch_finstep(L, s, 0);
+      launch_passB(L, s);
     }
     MSW_HIP(hipGetLastError());
-    poll(h);
-    if (h->sc_host->done) break;
-    if (h->sc_host->have_eval && (size_t)h->sc_host->iter + 1 >= max_iters) {  // the last evaluation's verdict ends the run
-      launch_finstep(h, 1);
+    poll(s);
+    if (s.sc_host->done) break;
+    if (s.sc_host->have_eval && (size_t)s.sc_host->iter + 1 >= max_iters) {  // the last evaluation's verdict ends the run
+      launch_finstep(L, s, 1);
       MSW_HIP(hipGetLastError());
-      poll(h);
-      if (h->sc_host->done) break;
+      poll(s);
+      if (s.sc_host->done) break;
     }
-    iters_done = (size_t)h->sc_host->iter;
+    iters_done = (size_t)s.sc_host->iter;
   }
 }
 
-void finish_solve(msw_core *h, double *theta_out, size_t *iters_out, double *bound_out) {
-  poll(h);
-  const uint32_t G = h->G;
+void finish_solve(const Resident &L, Solver &s, double *theta_out, size_t *iters_out, double *bound_out) {
+  poll(s);
+  const uint32_t G = L.G;
   int gerr = 0;
-  MSW_HIP(hipMemcpy(&gerr, h->guard_err.p, sizeof gerr, hipMemcpyDeviceToHost));
+  MSW_HIP(hipMemcpy(&gerr, s.guard_err.p, sizeof gerr, hipMemcpyDeviceToHost));
   if (gerr) {
-    MSW_HIP(hipMemset(h->guard_err.p, 0, sizeof gerr));
+    MSW_HIP(hipMemset(s.guard_err.p, 0, sizeof gerr));
     if (gerr == 2) throw Fail("internal: a workgroup's list of guarded equivalence classes overflowed");
     throw NumericFail("likelihood underflow: an equivalence class has zero probability under every group "
                       "(exp(a * log-likelihood) and the group weights underflow fp64 together)");
   }
   // (an EM run that was asked for no iteration leaves its initial bound, -inf: nothing is wrong)
-  if (h->sc_host->iter > 0 && !std::isfinite(h->sc_host->bound))
+  if (s.sc_host->iter > 0 && !std::isfinite(s.sc_host->bound))
     throw NumericFail("the evidence lower bound is not finite: the likelihood or the prior counts are out of range");
   if (theta_out) {
-    if (h->last_algo == MSW_ALGO_EM) {
-      MSW_HIP(hipMemcpy(theta_out, h->logth.p, G * sizeof(double), hipMemcpyDeviceToHost));  // theta of the last M-step
+    if (s.last_algo == MSW_ALGO_EM) {
+      MSW_HIP(hipMemcpy(theta_out, s.logth.p, G * sizeof(double), hipMemcpyDeviceToHost));  // theta of the last M-step
     } else {
       std::vector<double> nc(G);
-      MSW_HIP(hipMemcpy(nc.data(), h->Nc.p, G * sizeof(double), hipMemcpyDeviceToHost));
-      const double csum = h->sc_host->csum;
+      MSW_HIP(hipMemcpy(nc.data(), s.Nc.p, G * sizeof(double), hipMemcpyDeviceToHost));
+      const double csum = s.sc_host->csum;
       for (uint32_t g = 0; g < G; ++g) theta_out[g] = nc[g] / csum;
     }
   }
-  if (iters_out) *iters_out = (size_t)h->sc_host->iter;
-  if (bound_out) *bound_out = h->sc_host->bound;
-  h->have_solution = true;
+  if (iters_out) *iters_out = (size_t)s.sc_host->iter;
+  if (bound_out) *bound_out = s.sc_host->bound;
+  s.have_solution = true;
 }
 
-void collect_timing(msw_core *h) {
+void collect_timing(const Resident &L, Solver &s) {
   float ms = 0.f;
-  MSW_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->timing.solve_ms = ms;
-  h->timing.passA_ms = h->timing.passB_ms = 0.0;
-  if (h->profiling) {
+  MSW_HIP(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+  s.timing.solve_ms = ms;
+  s.timing.passA_ms = s.timing.passB_ms = 0.0;
+  if (s.profiling) {
     // launches enqueued after `done` was set return immediately; they are still counted
-    for (size_t i = 0; i < h->evA_used; ++i) {
-      MSW_HIP(hipEventElapsedTime(&ms, h->evA[i].first, h->evA[i].second));
-      h->timing.passA_ms += ms;
+    for (size_t i = 0; i < s.evA_used; ++i) {
+      MSW_HIP(hipEventElapsedTime(&ms, s.evA[i].first, s.evA[i].second));
+      s.timing.passA_ms += ms;
     }
-    for (size_t i = 0; i < h->evB_used; ++i) {
-      MSW_HIP(hipEventElapsedTime(&ms, h->evB[i].first, h->evB[i].second));
-      h->timing.passB_ms += ms;
+    for (size_t i = 0; i < s.evB_used; ++i) {
+      MSW_HIP(hipEventElapsedTime(&ms, s.evB[i].first, s.evB[i].second));
+      s.timing.passB_ms += ms;
     }
-    h->timing.collective_ms = 0.0;
-    for (size_t i = 0; i < h->evC_used; ++i) {
-      MSW_HIP(hipEventElapsedTime(&ms, h->evC[i].first, h->evC[i].second));
-      h->timing.collective_ms += ms;
+    s.timing.collective_ms = 0.0;
+    for (size_t i = 0; i < s.evC_used; ++i) {
+      MSW_HIP(hipEventElapsedTime(&ms, s.evC[i].first, s.evC[i].second));
+      s.timing.collective_ms += ms;
     }
-    h->timing.collectives = h->evC_used;
+    s.timing.collectives = s.evC_used;
   }
-  h->timing.iters = (uint64_t)h->sc_host->iter;
-  const uint64_t recsz = h->enc == kEncValue ? 12 : (h->wide() ? 8 : 4);
-  if (h->flavor == 0) {
+  s.timing.iters = (uint64_t)s.sc_host->iter;
+  const uint64_t recsz = L.enc == kEncValue ? 12 : (L.wide() ? 8 : 4);
+  if (L.flavor == 0) {
     // algorithmic bytes: every real cell record once + the per-EC count vector in
     // pass B; SELL padding, slice offsets and the L2-served second read of pass B are not counted
     // (slot tables that do not fit LDS are read from memory: every used 16-byte entry at least once per sweep)
     // (a hybrid area: the entries beyond its LDS-resident head)
-    const uint64_t tab = h->tlds ? 0ull : 16ull * (h->n_area - h->n_tab_lds);
-    h->timing.bytes_passA = h->nnz * recsz + tab;
-    h->timing.bytes_passB = h->nnz * recsz + 1ull * h->E + tab;  // + one byte per EC (its multiplicity)
+    const uint64_t tab = L.tlds ? 0ull : 16ull * (L.n_area - L.n_tab_lds);
+    s.timing.bytes_passA = L.nnz * recsz + tab;
+    s.timing.bytes_passB = L.nnz * recsz + 1ull * L.E + tab;  // + one byte per EC (its multiplicity)
   } else {
-    h->timing.bytes_passA = 8ull * h->E * h->G;
-    h->timing.bytes_passB = 8ull * h->E * h->G + 8ull * h->E;
+    s.timing.bytes_passA = 8ull * L.E * L.G;
+    s.timing.bytes_passB = 8ull * L.E * L.G + 8ull * L.E;
   }
 }
 
-void run_em(msw_core *h, size_t max_iters, int prec);
+void run_em(const Resident &L, Solver &s, size_t max_iters, int prec);
 
 // n more iterations of the fixed-iteration RCG solve that last ran on the handle: the state carries on
 // where it stood (no re-initialisation, no initial evaluation) -- what a benchmark's "W warm-up steps,
 // then exactly K timed steps" means for an iterative solver.
-void continue_impl(msw_core *h, size_t n_iters, double *theta_out, size_t *iters_out, double *bound_out) {
-  if (!h->have_solution || !h->fixed_iters || h->last_algo != MSW_ALGO_RCG)
+void continue_impl(const Resident &L, Solver &s, size_t n_iters, double *theta_out, size_t *iters_out, double *bound_out) {
+  if (!s.have_solution || !s.fixed_iters || s.last_algo != MSW_ALGO_RCG)
     throw Fail("msw_core_continue: needs a fixed-iteration RCG solve on the handle (msw_core_set_fixed_iters, msw_core_run)");
-  const size_t start = (size_t)h->sc_host->iter;
+  const size_t start = (size_t)s.sc_host->iter;
   if (n_iters == 0 || start + n_iters > (size_t)std::numeric_limits<int32_t>::max()) throw Fail("msw_core_continue: iteration count out of range");
-  h->timing = {};
-  h->evA_used = h->evB_used = h->evC_used = 0;
-  CollectiveScope cs(h);
-  hipLaunchKernelGGL(k_extend, dim3(1), dim3(1), 0, h->stream, h->sc.p, (int)n_iters);
-  MSW_HIP(hipEventRecord(h->ev0, h->stream));
-  run_rcg(h, start + n_iters, start);
-  MSW_HIP(hipEventRecord(h->ev1, h->stream));
-  finish_solve(h, theta_out, iters_out, bound_out);
-  collect_timing(h);
-  h->timing.iters = (uint64_t)h->sc_host->iter - start;
+  s.timing = {};
+  s.evA_used = s.evB_used = s.evC_used = 0;
+  CollectiveScope cs(s.collective);
+  hipLaunchKernelGGL(k_extend, dim3(1), dim3(1), 0, s.stream, s.sc.p, (int)n_iters);
+  MSW_HIP(hipEventRecord(s.ev0, s.stream));
+  run_rcg(L, s, start + n_iters, start);
+  MSW_HIP(hipEventRecord(s.ev1, s.stream));
+  finish_solve(L, s, theta_out, iters_out, bound_out);
+  collect_timing(L, s);
+  s.timing.iters = (uint64_t)s.sc_host->iter - start;
   cs.leave();
 }
 
-void run_impl(msw_core *h, double tol, size_t max_iters, int algo, int prec, double *theta_out,
+void run_impl(const Resident &L, Solver &s, double tol, size_t max_iters, int algo, int prec, double *theta_out,
               size_t *iters_out, double *bound_out) {
-  validate_solve(h, max_iters, algo, prec);
-  if (!h->prepared) throw Fail("msw_core_run: inputs not prepared (call msw_core_prepare)");
-  h->timing = {};
-  h->evA_used = h->evB_used = h->evC_used = 0;
-  CollectiveScope cs(h);  // from here on a failure strands the peers of a sharded solve (guarded())
-  begin_solve(h, tol, max_iters);
-  MSW_HIP(hipEventRecord(h->ev0, h->stream));
-  if (algo == MSW_ALGO_RCG) run_rcg(h, max_iters);
-  else run_em(h, max_iters, prec);
-  MSW_HIP(hipEventRecord(h->ev1, h->stream));
-  h->last_algo = algo;
-  finish_solve(h, theta_out, iters_out, bound_out);
-  collect_timing(h);
+  validate_solve(max_iters, algo, prec);
+  if (!s.prepared) throw Fail("msw_core_run: inputs not prepared (call msw_core_prepare)");
+  s.timing = {};
+  s.evA_used = s.evB_used = s.evC_used = 0;
+  CollectiveScope cs(s.collective);  // from here on a failure strands the peers of a sharded solve (guarded())
+  begin_solve(L, s, tol, max_iters);
+  MSW_HIP(hipEventRecord(s.ev0, s.stream));
+  if (algo == MSW_ALGO_RCG) run_rcg(L, s, max_iters);
+  else run_em(L, s, max_iters, prec);
+  MSW_HIP(hipEventRecord(s.ev1, s.stream));
+  s.last_algo = algo;
+  finish_solve(L, s, theta_out, iters_out, bound_out);
+  collect_timing(L, s);
   cs.leave();
 }
 
@@ -968,6 +1006,8 @@ int msw_core_create(int device, msw_handle *out) {
     h->device = device;
     h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     MSW_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->solver.stream = h->stream;
+    h->solver.n_cu = h->n_cu;
     hipLaunchKernelGGL(k_warm, dim3(1), dim3(1), 0, h->stream, (int *)nullptr);  // code object load: here, once per process
     MSW_HIP(hipGetLastError());
     MSW_HIP(hipStreamSynchronize(h->stream));
@@ -989,10 +1029,10 @@ void msw_core_destroy(msw_handle h) {
 
 int msw_core_shape(msw_handle h, size_t *n_groups, size_t *n_ecs, size_t *nnz) {
   return guarded(h, [&] {
-    if (h->flavor < 0) throw Fail("no likelihood resident");
-    if (n_groups) *n_groups = h->G;
-    if (n_ecs) *n_ecs = h->E;
-    if (nnz) *nnz = h->flavor == 0 ? h->nnz : (size_t)h->G * h->E;
+    if (h->lik.flavor < 0) throw Fail("no likelihood resident");
+    if (n_groups) *n_groups = h->lik.G;
+    if (n_ecs) *n_ecs = h->lik.E;
+    if (nnz) *nnz = h->lik.flavor == 0 ? h->lik.nnz : (size_t)h->lik.G * h->lik.E;
   });
 }
 
@@ -1099,30 +1139,31 @@ int msw_alignment_read_device(msw_handle h, const char *const *paths, size_t n_p
 int msw_core_layout_info(msw_handle h, msw_layout_info *out) {
   return guarded(h, [&] {
     if (!out) throw Fail("null out");
-    if (h->flavor != 0) throw Fail("msw_core_layout_info: no CSR-of-ECs likelihood resident");
+    const Resident &L = h->lik;
+    if (L.flavor != 0) throw Fail("msw_core_layout_info: no CSR-of-ECs likelihood resident");
     msw_layout_info li = {};
-    li.record_bytes = h->enc == kEncValue ? 12 : (h->wide() ? 8 : 4);
-    li.index_records = h->hybrid() ? 1 : 0;
-    li.groups_in_lds = h->glds ? 1 : 0;
-    li.table_in_lds = h->tlds ? 1 : 0;
-    li.passB_mode = h->gmodeB;
-    li.slot_entries = h->n_area;
-    li.slot_entries_in_lds = h->n_tab_lds;
-    li.n_slices = h->nslices;
-    li.n_long_ecs = h->n_long;
-    li.bank_scheduled = h->packed_scheduled ? 1 : 0;
-    li.passB_reg_cells = h->passB_rc8 ? 8 : kRegCells;
-    li.rows_over_8 = h->rows_over8;
-    std::vector<uint32_t> off((size_t)h->nslices + 1);
-    MSW_HIP(hipMemcpy(off.data(), h->slice_off.p, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    li.rows = off[h->nslices];
-    for (int c = 0; c < kSliceClasses; ++c) li.slices_by_lanes[c] = h->cls.s0[c + 1] - h->cls.s0[c];
-    for (uint32_t s2 = 0; s2 < h->nslices; ++s2) li.max_rows = std::max(li.max_rows, off[s2 + 1] - off[s2]);
-    if (h->hybrid()) {
-      std::vector<uint8_t> hot(std::max<uint32_t>(h->nslices, 1));
-      MSW_HIP(hipMemcpy(hot.data(), h->slice_hot.p, hot.size(), hipMemcpyDeviceToHost));
-      for (uint32_t s2 = 0; s2 < h->nslices; ++s2) li.rows_from_memory += (off[s2 + 1] - off[s2]) - hot[s2];
-    } else if (!h->tlds && h->enc != kEncValue) {
+    li.record_bytes = L.enc == kEncValue ? 12 : (L.wide() ? 8 : 4);
+    li.index_records = L.hybrid() ? 1 : 0;
+    li.groups_in_lds = L.glds ? 1 : 0;
+    li.table_in_lds = L.tlds ? 1 : 0;
+    li.passB_mode = L.gmodeB;
+    li.slot_entries = L.n_area;
+    li.slot_entries_in_lds = L.n_tab_lds;
+    li.n_slices = L.nslices;
+    li.n_long_ecs = L.n_long;
+    li.bank_scheduled = L.packed_scheduled ? 1 : 0;
+    li.passB_reg_cells = L.passB_rc8 ? 8 : kRegCells;
+    li.rows_over_8 = L.rows_over8;
+    std::vector<uint32_t> off((size_t)L.nslices + 1);
+    MSW_HIP(hipMemcpy(off.data(), L.slice_off.p, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    li.rows = off[L.nslices];
+    for (int c = 0; c < kSliceClasses; ++c) li.slices_by_lanes[c] = L.cls.s0[c + 1] - L.cls.s0[c];
+    for (uint32_t s2 = 0; s2 < L.nslices; ++s2) li.max_rows = std::max(li.max_rows, off[s2 + 1] - off[s2]);
+    if (L.hybrid()) {
+      std::vector<uint8_t> hot(std::max<uint32_t>(L.nslices, 1));
+      MSW_HIP(hipMemcpy(hot.data(), L.slice_hot.p, hot.size(), hipMemcpyDeviceToHost));
+      for (uint32_t s2 = 0; s2 < L.nslices; ++s2) li.rows_from_memory += (off[s2 + 1] - off[s2]) - hot[s2];
+    } else if (!L.tlds && L.enc != kEncValue) {
       li.rows_from_memory = li.rows;
     }
     *out = li;
@@ -1132,24 +1173,24 @@ int msw_core_layout_info(msw_handle h, msw_layout_info *out) {
 int msw_core_layout_hash(msw_handle h, uint64_t *hash_out) {
   return guarded(h, [&] {
     if (!hash_out) throw Fail("null out");
-    *hash_out = layout_hash(h);
+    *hash_out = layout_hash(h->lik);
   });
 }
 
 int msw_core_get_dense_logl(msw_handle h, double *L_out, size_t ld) {
-  return guarded(h, [&] { materialise_impl(h, L_out, ld, /*gamma=*/false, 0, h->E); });
+  return guarded(h, [&] { materialise_impl(h, L_out, ld, /*gamma=*/false, 0, h->lik.E); });
 }
 
 int msw_core_gamma(msw_handle h, double *gamma_out, size_t ld) {
   return guarded(h, [&] {
-    if (!h->have_solution) throw Fail("msw_core_gamma: no solve has run on this handle");
-    materialise_impl(h, gamma_out, ld, /*gamma=*/true, 0, h->E);
+    if (!h->solver.have_solution) throw Fail("msw_core_gamma: no solve has run on this handle");
+    materialise_impl(h, gamma_out, ld, /*gamma=*/true, 0, h->lik.E);
   });
 }
 
 int msw_core_gamma_block(msw_handle h, size_t ec_begin, size_t ec_end, double *gamma_out, size_t ld) {
   return guarded(h, [&] {
-    if (!h->have_solution) throw Fail("msw_core_gamma_block: no solve has run on this handle");
+    if (!h->solver.have_solution) throw Fail("msw_core_gamma_block: no solve has run on this handle");
     materialise_impl(h, gamma_out, ld, /*gamma=*/true, ec_begin, ec_end);
   });
 }
@@ -1182,47 +1223,47 @@ int msw_core_solve(msw_handle h, const double *logc, const double *alpha0, doubl
                    int algo, int prec, double *theta_out, size_t *iters_out, double *bound_out) {
   return guarded(h, [&] {
     if (!alpha0) throw Fail("msw_core_solve: null alpha0");
-    prepare_inputs(h, logc, nullptr, alpha0);
-    run_impl(h, tol, max_iters, algo, prec, theta_out, iters_out, bound_out);
+    prepare_inputs(h->lik, h->solver, logc, nullptr, alpha0);
+    run_impl(h->lik, h->solver, tol, max_iters, algo, prec, theta_out, iters_out, bound_out);
   });
 }
 
 int msw_core_prepare(msw_handle h, const double *logc, const double *alpha0) {
   return guarded(h, [&] {
     if (!alpha0) throw Fail("msw_core_prepare: null alpha0");
-    prepare_inputs(h, logc, nullptr, alpha0);
+    prepare_inputs(h->lik, h->solver, logc, nullptr, alpha0);
   });
 }
 
 int msw_core_run(msw_handle h, double tol, size_t max_iters, int algo, int prec, double *theta_out,
                  size_t *iters_out, double *bound_out) {
-  return guarded(h, [&] { run_impl(h, tol, max_iters, algo, prec, theta_out, iters_out, bound_out); });
+  return guarded(h, [&] { run_impl(h->lik, h->solver, tol, max_iters, algo, prec, theta_out, iters_out, bound_out); });
 }
 
 int msw_core_continue(msw_handle h, size_t n_iters, double *theta_out, size_t *iters_out, double *bound_out) {
-  return guarded(h, [&] { continue_impl(h, n_iters, theta_out, iters_out, bound_out); });
+  return guarded(h, [&] { continue_impl(h->lik, h->solver, n_iters, theta_out, iters_out, bound_out); });
 }
 
 int msw_core_set_trace_theta(msw_handle h, size_t n_iters) {
   return guarded(h, [&] {
     if (n_iters > (size_t)kMaxTrace) throw Fail("trace_theta: at most 4096 iterations");
-    h->trace_theta = n_iters;
+    h->solver.trace_theta = n_iters;
   });
 }
 
 int msw_core_trace(msw_handle h, size_t n, double *bound, double *newnorm, double *beta,
                    int32_t *didreset, double *theta_trace, size_t *n_out) {
   return guarded(h, [&] {
-    if (!h->have_solution) throw Fail("msw_core_trace: no solve has run on this handle");
-    size_t have = std::min<size_t>((size_t)h->sc_host->iter, kMaxTrace);
+    if (!h->solver.have_solution) throw Fail("msw_core_trace: no solve has run on this handle");
+    size_t have = std::min<size_t>((size_t)h->solver.sc_host->iter, kMaxTrace);
     n = std::min(n, have);
-    if (bound) MSW_HIP(hipMemcpy(bound, h->tr_bound.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (newnorm) MSW_HIP(hipMemcpy(newnorm, h->tr_newnorm.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta) MSW_HIP(hipMemcpy(beta, h->tr_beta.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (didreset) MSW_HIP(hipMemcpy(didreset, h->tr_reset.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (bound) MSW_HIP(hipMemcpy(bound, h->solver.tr_bound.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (newnorm) MSW_HIP(hipMemcpy(newnorm, h->solver.tr_newnorm.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta) MSW_HIP(hipMemcpy(beta, h->solver.tr_beta.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (didreset) MSW_HIP(hipMemcpy(didreset, h->solver.tr_reset.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (theta_trace) {
-      const size_t nt = std::min(n, h->trace_theta);
-      if (nt) MSW_HIP(hipMemcpy(theta_trace, h->tr_theta.p, nt * h->G * sizeof(double), hipMemcpyDeviceToHost));
+      const size_t nt = std::min(n, h->solver.trace_theta);
+      if (nt) MSW_HIP(hipMemcpy(theta_trace, h->solver.tr_theta.p, nt * h->lik.G * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (n_out) *n_out = n;
   });
@@ -1409,10 +1450,10 @@ int msw_core_set_comm(msw_handle h, msw_comm_t comm) {
 }
 
 int msw_core_set_profiling(msw_handle h, int enabled) {
-  return guarded(h, [&] { h->profiling = enabled != 0; });
+  return guarded(h, [&] { h->solver.profiling = enabled != 0; });
 }
 int msw_core_set_fixed_iters(msw_handle h, int enabled) {
-  return guarded(h, [&] { h->fixed_iters = enabled != 0; });
+  return guarded(h, [&] { h->solver.fixed_iters = enabled != 0; });
 }
 int msw_core_set_pack_schedule(msw_handle h, int enabled) {
   return guarded(h, [&] { h->pack_schedule = enabled != 0; });
@@ -1422,19 +1463,19 @@ int msw_core_set_option(msw_handle h, int option, double value) {
     switch (option) {
       case MSW_OPT_CHECK_EVERY:
         if (!(value >= 1.0 && value <= 65536.0) || value != std::floor(value)) throw Fail("MSW_OPT_CHECK_EVERY: an integer in [1, 65536]");
-        h->opts.check_every = (int32_t)value;
+        h->solver.opts.check_every = (int32_t)value;
         break;
       case MSW_OPT_INIT_BOUND:
         if (std::isnan(value) || value == INFINITY) throw Fail("MSW_OPT_INIT_BOUND: a number below +inf");
-        h->opts.init_bound = value;
+        h->solver.opts.init_bound = value;
         break;
       case MSW_OPT_EM_PRIOR:
         if (value != 0.0 && value != 1.0) throw Fail("MSW_OPT_EM_PRIOR: 0 (MAP) or 1 (ML)");
-        h->opts.em_prior = (int32_t)value;
+        h->solver.opts.em_prior = (int32_t)value;
         break;
       case MSW_OPT_EM_STOP:
         if (value != 0.0 && value != 1.0) throw Fail("MSW_OPT_EM_STOP: 0 (log-likelihood gain) or 1 (largest move of a weight)");
-        h->opts.em_stop = (int32_t)value;
+        h->solver.opts.em_stop = (int32_t)value;
         break;
       default: throw Fail("msw_core_set_option: unknown option id");
     }
@@ -1444,10 +1485,10 @@ int msw_core_get_option(msw_handle h, int option, double *value) {
   return guarded(h, [&] {
     if (!value) throw Fail("null out");
     switch (option) {
-      case MSW_OPT_CHECK_EVERY: *value = h->opts.check_every; break;
-      case MSW_OPT_INIT_BOUND: *value = h->opts.init_bound; break;
-      case MSW_OPT_EM_PRIOR: *value = h->opts.em_prior; break;
-      case MSW_OPT_EM_STOP: *value = h->opts.em_stop; break;
+      case MSW_OPT_CHECK_EVERY: *value = h->solver.opts.check_every; break;
+      case MSW_OPT_INIT_BOUND: *value = h->solver.opts.init_bound; break;
+      case MSW_OPT_EM_PRIOR: *value = h->solver.opts.em_prior; break;
+      case MSW_OPT_EM_STOP: *value = h->solver.opts.em_stop; break;
       default: throw Fail("msw_core_get_option: unknown option id");
     }
   });
@@ -1455,7 +1496,7 @@ int msw_core_get_option(msw_handle h, int option, double *value) {
 int msw_core_last_timing(msw_handle h, msw_timing *out) {
   return guarded(h, [&] {
     if (!out) throw Fail("null out");
-    *out = h->timing;
+    *out = h->solver.timing;
   });
 }
 
@@ -1476,10 +1517,10 @@ int msw_debug_stamps(msw_handle h, uint64_t *out, int clear) {
 int msw_core_guarded_visits(msw_handle h, uint64_t *out) {
   return guarded(h, [&] {
     if (!out) throw Fail("null out");
-    if (h->flavor != 0) throw Fail("msw_core_guarded_visits: no CSR-of-ECs likelihood resident");
+    if (h->lik.flavor != 0) throw Fail("msw_core_guarded_visits: no CSR-of-ECs likelihood resident");
     unsigned long long v = 0;
     MSW_HIP(hipStreamSynchronize(h->stream));
-    MSW_HIP(hipMemcpy(&v, h->guard_visits.p, sizeof v, hipMemcpyDeviceToHost));
+    MSW_HIP(hipMemcpy(&v, h->solver.guard_visits.p, sizeof v, hipMemcpyDeviceToHost));
     *out = v;
   });
 }

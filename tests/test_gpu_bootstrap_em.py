@@ -194,6 +194,54 @@ def test_replicates_in_flight_across_likelihood_changes(gpu_core, monkeypatch):
     both(w, int(w.sum()), 70)
 
 
+def test_bootstrap_keeps_the_handles_solve_and_not_its_settings(monkeypatch):
+    """The replicates run beside the handle's own solve: gamma, the trace, the timing record and the guarded visits
+    after msw_core_bootstrap still describe the solve before it (the drivers write --write-probs after the
+    replicates).  And the replicates do not take the handle's fixed_iters, profiling or trace_theta: they solve to
+    tol whatever those say."""
+    from msweep_amd.core import Core
+    p = synth.make_csr_problem(20000, 40, seed=61, max_other=6)
+    G, n, max_iters = 40, 12, 5000
+    alpha0 = np.ones(G)
+    w = p["ec_counts"].astype(np.uint32)
+    draws = int(w.sum())
+
+    def state(core):
+        return core.gamma(), core.trace(n, with_theta=True), core.last_timing(), core.guarded_visits()
+
+    def assert_same_state(a, b):
+        np.testing.assert_array_equal(a[0], b[0])
+        assert a[1].keys() == b[1].keys()
+        for k in a[1]:
+            np.testing.assert_array_equal(a[1][k], b[1][k])
+        assert a[2] == b[2] and a[3] == b[3]
+
+    with Core(0) as core:
+        lik = from_grouped_counts(core, p["rowptr"], p["grp"], p["cnt"], p["ec_counts"], p["group_sizes"])
+        core.set_profiling(True)
+        core.set_trace_theta(n)
+        res = core.solve(lik.log_counts(), alpha0, max_iters=max_iters)
+        assert n < res["iters"] < max_iters
+        before = state(core)
+        assert before[1]["n"] == n and before[2]["passA_ms"] > 0.0
+        core.set_fixed_iters(True)
+        reps = {}
+        for streams in ("1", "4"):
+            monkeypatch.setenv("MSWEEP_BOOTSTRAP_STREAMS", streams)
+            reps[streams] = core.bootstrap(w, 3, draws, 0, 4, alpha0, max_iters=max_iters)
+            assert_same_state(state(core), before)
+        core.set_fixed_iters(False)
+        core.set_profiling(False)
+        core.set_trace_theta(0)
+        for streams in ("1", "4"):
+            monkeypatch.setenv("MSWEEP_BOOTSTRAP_STREAMS", streams)
+            theta, iters = core.bootstrap(w, 3, draws, 0, 4, alpha0, max_iters=max_iters)
+            np.testing.assert_array_equal(theta, reps[streams][0])
+            np.testing.assert_array_equal(iters, reps[streams][1])
+            assert np.all(iters < max_iters)
+        assert reps["1"][1].tolist() == reps["4"][1].tolist()
+
+
 
 def _float_problem(R, G, seed, max_other):
     p = synth.make_csr_problem(R, G, seed=seed, max_other=max_other)

@@ -117,7 +117,7 @@ def test_em_check_every(core_opts, oracle, prob):
 
 
 def test_options_reach_the_bootstrap_replicates(core_opts, oracle, prob):
-    """the replicates run on solver states of their own (host_bootstrap.inc share_likelihood): they inherit the options"""
+    """the replicates run on solver states of their own (host_bootstrap.inc bootstrap_impl): they inherit the options"""
     p, G = prob, 80
     alpha0 = np.ones(G)
     from_grouped_counts(core_opts, p["rowptr"], p["grp"], p["cnt"], p["ec_counts"], p["group_sizes"])

@@ -23,7 +23,7 @@ for R, G, B in CASES:
             os.environ.pop("MSWEEP_BOOTSTRAP_STREAMS", None)
         else:
             os.environ["MSWEEP_BOOTSTRAP_STREAMS"] = n
-        core.bootstrap(w, 42, draws, 0, 2, np.ones(G))            # warm: streams, clones, tables
+        core.bootstrap(w, 42, draws, 0, 2, np.ones(G))            # warm: streams, workers, tables
         t = time.perf_counter(); th, it = core.bootstrap(w, 42, draws, 0, B, np.ones(G)); dt = time.perf_counter() - t
         if ref is None:
             ref = th
