@@ -29,10 +29,13 @@ enum { MSW_ALGO_RCG = 0, MSW_ALGO_EM = 1 };
  * argument).  MSW_PREC_FLOAT (round 5) is REAL fp32 arithmetic (msweep_amd/csrc/em_f32_kernels.hpp): likelihood values,
  * weights, row sums and quotients in fp32, the log-likelihood rounded to float once per iteration for the stop rule
  * (which is why a float run stops after a few hundred iterations where double reaches --max-iters, as the reference's
- * does: docs/gpubenchmarks.md:20-22), column sums in exact 64-bit fixed point.  Served by fp32 kernels for 4-byte
- * offset records with table and group vectors in LDS, up to 6144 groups, one GPU; other layouts (8-byte / index /
- * value records, dense matrices without background structure, EC-sharded solves) run the fp64 kernels under
- * MSW_PREC_FLOAT as until round 4 -- msw_timing::em_float_kernels says which it was. */
+ * does: docs/gpubenchmarks.md:20-22), column sums in exact 64-bit fixed point.  Served by fp32 kernels on one GPU, for
+ * likelihoods in CSR-of-ECs form with at most 6144 groups whose group vectors the sweeps keep in LDS, laid out as
+ * 4-byte offset records with the whole slot table in LDS, or as index records (the layout of groupings with sizes up
+ * to hundreds, whose fp64 slot table does not fit LDS) whenever the float image -- 4 bytes per slot-area entry, 12 per
+ * group -- fits the 160 KB of LDS.  Other layouts (8-byte / value records, index records beyond that, dense matrices
+ * without background structure, EC-sharded solves) run the fp64 kernels under MSW_PREC_FLOAT as until round 4 --
+ * msw_timing::em_float_kernels says which it was. */
 enum { MSW_PREC_DOUBLE = 0, MSW_PREC_FLOAT = 1 };
 
 /* ---- lifetime ---------------------------------------------------------------------- */

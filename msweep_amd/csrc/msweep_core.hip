@@ -623,17 +623,26 @@ void launch_passA(const Resident &L, Solver &s) {
   s.timing.passA_launches++;
 }
 
-// --emprecision float: the fp32 sweep of em_f32_kernels.hpp (run_em decides; one persistent workgroup per CU)
+// --emprecision float: the fp32 sweeps of em_f32_kernels.hpp (run_em decides; one persistent workgroup per CU).
+// Served: one GPU, the CSR flavour, the group vectors in LDS, at most kStepRegs * 1024 groups, and either offset records
+// with the whole slot table in LDS or index records (the hybrid area, whatever part of it the fp64 images hold) whose
+// FLOAT image -- 4 bytes per entry of the whole area, 12 per group -- fits LDS.
 bool em_f32_layout_ok(const Resident &L, const Solver &s) {
-  return kFx && L.flavor == 0 && L.enc == kEncNarrow && L.glds && L.tlds && !s.comm() && L.n_tab_lds == L.n_area &&
-         L.G <= (uint32_t)(kStepRegs * 1024) && em_f32_lds_bytes(L.n_tab_lds, L.G) <= kLdsMax &&
-         !getenv("MSWEEP_EM_FLOAT_AS_DOUBLE");  // (developer switch: the fp64 kernels under MSW_PREC_FLOAT, as until round 4)
+  if (!kFx || L.flavor != 0 || !L.glds || s.comm() || L.G > (uint32_t)(kStepRegs * 1024)) return false;
+  if (getenv("MSWEEP_EM_FLOAT_AS_DOUBLE")) return false;  // (developer switch: the fp64 kernels under MSW_PREC_FLOAT, as until round 4)
+  if (L.enc == kEncNarrow)
+    return L.tlds && L.n_tab_lds == L.n_area && em_f32_lds_bytes(L.n_tab_lds, L.G) <= kLdsMax;
+  // (shift <= 30: the two shifts that leave 4 * entry of a record, em_f32_kernels.hpp F32Form)
+  if (L.hybrid()) return L.dec.shift <= 30 && em_f32_idx_lds_bytes(L.n_area, L.G) <= kLdsMax;
+  return false;
 }
 void launch_em_passB_f32(const Resident &L, Solver &s) {
-  const size_t lds = em_f32_lds_bytes(L.n_tab_lds, L.G);
+  const bool idx = L.hybrid();
+  const size_t lds = idx ? em_f32_idx_lds_bytes(L.n_area, L.G) : em_f32_lds_bytes(L.n_tab_lds, L.G);
   const bool ml = L.cls.s0[kSliceClasses - 1] > 0;
-  auto k = ml ? k_em_passB_f32<true> : k_em_passB_f32<false>;
-  prepare_sweep(k, lds, s.lds_attr[2][30 + (ml ? 1 : 0)]);
+  auto k = idx ? (ml ? k_em_passB_f32_idx<true> : k_em_passB_f32_idx<false>)
+               : (ml ? k_em_passB_f32<true> : k_em_passB_f32<false>);
+  prepare_sweep(k, lds, s.lds_attr[2][30 + (idx ? 2 : 0) + (ml ? 1 : 0)]);
   hipLaunchKernelGGL(k, dim3(L.nblk), dim3(1024), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p, s.e32.p, s.tab32.p,
                      s.partAcc.p, s.partS.p, guard_view(L, s));
 }
