@@ -213,6 +213,38 @@ struct msw_alignment;
 int msw_core_bin_reads_aln(msw_handle h, struct msw_alignment *a, const uint32_t *targets, const double *thresholds,
                            size_t n_targets, uint64_t *bin_ptr, uint32_t *reads_out, double *log_thr_out);
 
+/* The text of the matrix outputs, formatted on the device (text_kernels.hpp): the lines of the ECs [ec_begin, ec_end)
+ * as contiguous bytes in EC order, every cell printed as the reference's default `ostream <<` prints a double --
+ * printf("%g"), byte for byte (g6_format.hpp).  Only the bytes cross the link; nothing is sized G x E.
+ *   MSW_TEXT_PROBS   needs a solve; no line_prefix.  Line j: dec(j), then '\t' g6(exp(gamma(g, j))) per group, then
+ *                    n_zero_cols times "\t0", then '\n' (Sample::write_probs, src/Sample.cpp:63-85,154-186).  exp is
+ *                    the device's: against the host's exp a cell can differ where a rounding boundary of the six
+ *                    digits lies between two neighbouring doubles.
+ *   MSW_TEXT_LOGL    line_prefix[j - ec_begin] (the EC's read count) required, n_zero_cols == 0.  Line j: dec(prefix),
+ *                    then '\t' g6(L(g, j)) per group, then '\n' (include/Likelihood.hpp:255-273); L = the bits
+ *                    msw_core_get_dense_logl returns.
+ *   MSW_TEXT_BITSEQ  no line_prefix, n_zero_cols == 0.  Per EC the part of the BitSeq line after the read id:
+ *                    dec(G + 1) ' ', then dec(g + 1) ' ' g6(L(g, j)) ' ' per group, then "0 -10000.00\n"
+ *                    (include/Likelihood.hpp:295-305).
+ * *text_out points into a pinned host buffer owned by the handle, valid until the next call on the handle; *len_out is
+ * its length.  n_host_cells_out (may be NULL): cells the host had to format (values the device routine leaves
+ * undecided).  Refused (non-zero, msw_last_error; the handle stays usable): PROBS before a solve, a prefix missing or
+ * superfluous, zero columns outside PROBS, a range out of bounds, and a range whose worst-case text
+ * -- 20 + 14 G + 2 n_zero_cols + 12 bytes per line (BITSEQ: the group numbers on top) -- exceeds 1 GiB: the message
+ * says how many classes fit. */
+enum { MSW_TEXT_PROBS = 0, MSW_TEXT_LOGL = 1, MSW_TEXT_BITSEQ = 2 };
+int msw_core_text_block(msw_handle h, int what, size_t ec_begin, size_t ec_end,
+                        const uint64_t *line_prefix, size_t n_zero_cols,
+                        const char **text_out, size_t *len_out, size_t *n_host_cells_out);
+/* The formatter alone, its test and diagnostic entry: the n host doubles x through the same kernels, each followed by
+ * '\n'.  text_out / len_out / n_host_out as above. */
+int msw_core_format_g6(msw_handle h, const double *x, size_t n,
+                       const char **text_out, size_t *len_out, size_t *n_host_out);
+/* Measurement hook (tools/text_timing.py): device time of the text kernels of the last of those two calls -- length
+ * pass, scan and write pass, from events on the handle's stream; the materialisation of the block and the copy of the
+ * bytes are not in it -- and the bytes of text the kernels wrote (undecided cells still 13 blanks wide). */
+int msw_core_last_text_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out);
+
 /* Per-iteration diagnostics of the last solve (what rcgpar logs every 5th iteration to
  * the verbose stream, src/mSWEEP.cpp:198): arrays of length n (<= max recorded, 4096);
  * theta_trace is n x G or NULL.  Returns the number of iterations recorded via *n_out. */

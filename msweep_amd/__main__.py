@@ -1,14 +1,18 @@
 """`python -m msweep_amd` -- the estimation part of mSWEEP's command line (src/mSWEEP.cpp:68-148)
 over the MI355X core: Themisto plaintext in, `<prefix>_abundances.txt` out, and with --bin-reads the
 mGEMS bins `<dir>/<group>.bin` (src/mSWEEP.cpp:437-469; the bin pass runs on the device, msweep_amd/binning.py
-holds the driver's side).  Compression of the outputs is out of scope."""
+holds the driver's side).  The matrix outputs -- --write-probs / --print-probs, --write-likelihood,
+--write-likelihood-bitseq -- are formatted on the device (Core.text_block): only their bytes come to the host.
+Compression of the outputs is out of scope."""
 import argparse
+import math
+import os
 import sys
 
 import numpy as np
 
 from . import binning, parallel
-from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, Core, MswError
+from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
 from .likelihood import from_device_alignment, from_dense
 from .reference import read_reference
 from .sample import BootstrapSample, PlainSample
@@ -39,6 +43,7 @@ def parse(argv):
     ap.add_argument("--write-probs", action="store_true")
     ap.add_argument("--print-probs", action="store_true")
     ap.add_argument("--write-likelihood", action="store_true")
+    ap.add_argument("--write-likelihood-bitseq", action="store_true")
     ap.add_argument("--read-likelihood")
     ap.add_argument("--no-fit-model", action="store_true")
     ap.add_argument("--bin-reads", action="store_true")
@@ -61,20 +66,98 @@ def read_likelihood_file(path, n_groups):
     return np.array(counts, np.uint64), np.ascontiguousarray(np.array(cols).T)
 
 
-def write_likelihood_file(f, ec_counts, L):
-    for j in range(L.shape[1]):
-        f.write(str(int(ec_counts[j])) + "\t" + "\t".join("%g" % x for x in L[:, j]) + "\n")
+def host_text():
+    """MSWEEP_HOST_TEXT=1 (developer switch): the matrices come to the host as doubles and are formatted here, cell by
+    cell, as before the device formatter -- the other side of its A/B and of tests/test_gpu_cli_text.py."""
+    return os.environ.get("MSWEEP_HOST_TEXT", "") == "1"
+
+
+def text_block_ecs(n_groups, n_zero=0, cell=14):
+    """Classes per Core.text_block call: 8192, fewer when the worst-case text of a block (20 + cell * G + 2 n_zero + 12
+    bytes per line) would exceed 256 MiB; MSWEEP_TEXT_BLOCK=n (developer switch) overrides it."""
+    n = int(os.environ.get("MSWEEP_TEXT_BLOCK", "0") or 0)
+    if n > 0:
+        return n
+    return max(1, min(8192, (256 << 20) // (20 + cell * n_groups + 2 * n_zero + 12)))
+
+
+def _bytes_out(f):
+    """where bytes go on a text stream (files opened here are binary already)"""
+    if hasattr(f, "buffer"):
+        f.flush()
+        return f.buffer
+    return f
+
+
+def write_likelihood_file(f, ec_counts, lik):
+    """--write-likelihood (include/Likelihood.hpp:255-273): "count \\t L(0,j) ... L(G-1,j)" per class, the lines
+    formatted on the device (TEXT_LOGL): no G x E matrix on the host.  MSWEEP_HOST_TEXT=1: the dense matrix, here."""
+    if host_text():
+        L = lik.log_mat()
+        for j in range(L.shape[1]):
+            f.write((str(int(ec_counts[j])) + "\t" + "\t".join("%g" % x for x in L[:, j]) + "\n").encode())
+        return
+    E, block = lik.n_ecs, text_block_ecs(lik.n_groups)
+    counts = np.asarray(ec_counts, np.uint64)
+    for e0 in range(0, E, block):
+        e1 = min(E, e0 + block)
+        f.write(lik.core.text_block(TEXT_LOGL, e0, e1, line_prefix=counts[e0:e1]))
+
+
+def bitseq_total(ec_counts):
+    """Ntotal / Nmap as the reference forms them (include/Likelihood.hpp:280-289): std::accumulate starts from an `int`
+    0 with a lambda that returns a double, so the sum is truncated to an integer after every class -- and exp(log c)
+    can fall just below c (a lone class of 5 reads gives 4).  Ntotal can therefore be below the number of reads."""
+    acc = 0
+    for c in ec_counts:
+        acc = int(float(acc) + math.exp(math.log(float(c))))
+    return acc
+
+
+def write_likelihood_bitseq(f, ec_counts, lik):
+    """--write-likelihood-bitseq (include/Likelihood.hpp:275-311): five header lines, then one line per READ of every
+    class -- the read id (from 1, never restarting) and the class's tail, which the device formats once per class
+    (TEXT_BITSEQ)."""
+    G, E = lik.n_groups, lik.n_ecs
+    total = bitseq_total(ec_counts)
+    f.write((f"# Ntotal {total}\n# Nmap {total}\n# M {G}\n# LOGFORMAT (probabilities saved on log scale.)\n"
+             "# r_name num_alignments (tr_id prob )^*{num_alignments}\n").encode())
+    on_host = host_text()
+    L = lik.log_mat() if on_host else None
+    block = 8192 if on_host else text_block_ecs(G, 0, 15 + len(str(G + 1)))
+    read_id = 1
+    for e0 in range(0, E, block):
+        e1 = min(E, e0 + block)
+        if on_host:
+            tails = [(f"{G + 1} " + "".join(f"{g + 1} {'%g' % x} " for g, x in enumerate(L[:, j])) + "0 -10000.00").encode()
+                     for j in range(e0, e1)]
+        else:
+            tails = lik.core.text_block(TEXT_BITSEQ, e0, e1).split(b"\n")[:-1]
+        if len(tails) != e1 - e0:
+            raise RuntimeError("the BitSeq text of a block ends before its last class")
+        for j, tail in zip(range(e0, e1), tails):
+            c = int(ec_counts[j])
+            f.write(b"".join(str(read_id + k).encode() + b" " + tail + b"\n" for k in range(c)))
+            read_id += c
 
 
 def write_probs(of, names, zero_names, core, block=8192):
-    """Sample::write_probs[2] (src/Sample.cpp:63-85,154-186), one line per EC, streamed from the device in
-    blocks of ECs (msw_core_gamma_block): the G x E matrix is never held, here or there."""
+    """Sample::write_probs[2] (src/Sample.cpp:63-85,154-186), one line per EC.  The lines are formatted on the device a
+    block of classes at a time (TEXT_PROBS); with MSWEEP_HOST_TEXT=1 the block comes as doubles (msw_core_gamma_block)
+    and is formatted here.  The G x E matrix is never held, here or there."""
     of.write("ec_id\t" + "\t".join(list(names) + list(zero_names)) + "\n")
-    E = core.shape()[1]
-    for e0 in range(0, E, block):
-        probs = np.exp(core.gamma_block(e0, min(E, e0 + block)))
-        for jj in range(probs.shape[1]):
-            of.write(str(e0 + jj) + "\t" + "\t".join(["%g" % x for x in probs[:, jj]] + ["0"] * len(zero_names)) + "\n")
+    G, E = core.shape()[:2]
+    if host_text():
+        for e0 in range(0, E, block):
+            probs = np.exp(core.gamma_block(e0, min(E, e0 + block)))
+            for jj in range(probs.shape[1]):
+                of.write(str(e0 + jj) + "\t" + "\t".join(["%g" % x for x in probs[:, jj]] + ["0"] * len(zero_names)) + "\n")
+    else:
+        raw = _bytes_out(of)
+        block = text_block_ecs(G, len(zero_names))
+        for e0 in range(0, E, block):
+            raw.write(core.text_block(TEXT_PROBS, e0, min(E, e0 + block), n_zero_cols=len(zero_names)))
+        raw.flush()
     of.write("\n")
     of.flush()
 
@@ -177,11 +260,20 @@ def main(argv=None):
     except (MswError, RuntimeError, OSError, ValueError) as ex:
         sys.stderr.write(f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
         return 1
-    if a.write_likelihood:
-        # --write-likelihood (include/Likelihood.hpp:255-273), default ostream precision; the file is
-        # <prefix>_likelihoods.tsv (src/OutfileDesignator.cpp:67-74; the flag's help text says .txt)
-        with open(f"{a.prefix}_likelihoods.tsv" if a.prefix else "likelihoods.tsv", "w") as f:
-            write_likelihood_file(f, ec_counts, lik.log_mat())
+    try:
+        if a.write_likelihood_bitseq:
+            # both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376); <prefix>_bitseq_likelihoods.tsv
+            # (src/OutfileDesignator.cpp:67-74)
+            with open(f"{a.prefix}_bitseq_likelihoods.tsv" if a.prefix else "bitseq_likelihoods.tsv", "wb") as f:
+                write_likelihood_bitseq(f, ec_counts, lik)
+        elif a.write_likelihood:
+            # --write-likelihood (include/Likelihood.hpp:255-273), default ostream precision; the file is
+            # <prefix>_likelihoods.tsv (src/OutfileDesignator.cpp:67-74; the flag's help text says .txt)
+            with open(f"{a.prefix}_likelihoods.tsv" if a.prefix else "likelihoods.tsv", "wb") as f:
+                write_likelihood_file(f, ec_counts, lik)
+    except (MswError, RuntimeError, OSError) as ex:
+        sys.stderr.write(f"Writing the likelihood to file failed:\n  {ex}\nexiting\n")
+        return 1
     if a.no_fit_model:
         core.close()
         return 0

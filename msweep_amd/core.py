@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MSWEEP_CORE_LIB") or os.path.join(_HERE, "libmsweep_c
 
 ALGO_RCG, ALGO_EM = 0, 1
 PREC_DOUBLE, PREC_FLOAT = 0, 1
+TEXT_PROBS, TEXT_LOGL, TEXT_BITSEQ = 0, 1, 2      # msw_core_text_block
 # msw_core_set_option ids (include/msweep_core.h): the knobs of rcgpar's loops that are restated from memory
 OPT_CHECK_EVERY, OPT_INIT_BOUND, OPT_EM_PRIOR, OPT_EM_STOP = 0, 1, 2, 3
 _OPTS = {"check_every": OPT_CHECK_EVERY, "init_bound": OPT_INIT_BOUND, "em_prior": OPT_EM_PRIOR, "em_stop": OPT_EM_STOP}
@@ -34,6 +35,7 @@ EXPORTS = [
     "msw_comm_size", "msw_comm_rccl_count", "msw_comm_allgather", "msw_comm_allreduce", "msw_comm_create_shm", "msw_core_continue", "msw_core_gamma_block",
     "msw_core_last_bootstrap_timing", "msw_core_layout_info", "msw_core_guarded_visits", "msw_core_set_pack_schedule",
     "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
+    "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
 ]
 
 
@@ -125,6 +127,9 @@ def load_library():
     L.msw_core_gamma_block.argtypes = [vp, sz, sz, vp, sz]
     L.msw_core_bin_reads.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
     L.msw_core_bin_reads_aln.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
+    L.msw_core_text_block.argtypes = [vp, C.c_int, sz, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.msw_core_format_g6.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.msw_core_last_text_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64)]
     L.msw_core_trace.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.msw_core_set_trace_theta.argtypes = [vp, sz]
     L.msw_core_bootstrap.argtypes = [vp, vp, C.c_int32, sz, sz, sz, vp, dp, sz, C.c_int, C.c_int, vp, vp]
@@ -455,6 +460,36 @@ class Core:
         out = np.empty((G, max(w, 0)))
         self._check(self._L.msw_core_gamma_block(self._h, int(ec_begin), int(ec_end), _ptr(out), max(w, 1)))
         return out
+
+    def text_block(self, what, ec_begin, ec_end, line_prefix=None, n_zero_cols=0, with_host_cells=False):
+        """The lines of the ECs [ec_begin, ec_end) of a matrix output, formatted on the device (msw_core_text_block):
+        TEXT_PROBS (--write-probs), TEXT_LOGL (--write-likelihood; line_prefix = the read count of every class) or
+        TEXT_BITSEQ (the BitSeq line after the read id).  Returns the bytes -- a copy: the library's buffer lives until
+        the next call only -- and, with_host_cells, how many cells the host had to format."""
+        if line_prefix is not None:
+            line_prefix = _arr(line_prefix, np.uint64)
+            if len(line_prefix) != int(ec_end) - int(ec_begin):
+                raise MswError("text_block: one line_prefix per class of the range")
+        p, n, nh = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._check(self._L.msw_core_text_block(self._h, int(what), int(ec_begin), int(ec_end), _ptr(line_prefix),
+                                                int(n_zero_cols), C.byref(p), C.byref(n), C.byref(nh)))
+        text = C.string_at(p.value, n.value) if n.value else b""
+        return (text, nh.value) if with_host_cells else text
+
+    def format_g6(self, x, with_host_cells=False):
+        """printf("%g") of every double of x on the device, one per line (msw_core_format_g6: the formatter's test and
+        diagnostic entry)."""
+        x = _arr(x, np.float64).ravel()
+        p, n, nh = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._check(self._L.msw_core_format_g6(self._h, _ptr(x) if len(x) else None, len(x), C.byref(p), C.byref(n), C.byref(nh)))
+        text = C.string_at(p.value, n.value) if n.value else b""
+        return (text, nh.value) if with_host_cells else text
+
+    def last_text_timing(self):
+        """(device ms of the text kernels, bytes they wrote) of the last text_block / format_g6 call"""
+        ms, nb = C.c_double(), C.c_uint64()
+        self._check(self._L.msw_core_last_text_timing(self._h, C.byref(ms), C.byref(nb)))
+        return ms.value, nb.value
 
     def bin_reads(self, ec_rptr, ec_reads, targets, thresholds, want_reads=True):
         """mGEMS read binning of the last solve on the device (msw_core_bin_reads): the reads of EC j go to bin k when

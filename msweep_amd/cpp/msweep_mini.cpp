@@ -6,7 +6,8 @@
 // PlainSample / BootstrapSample::write_abundances[2] (src/PlainSample.cpp:32-71,
 // src/BootstrapSample.cpp:75-130), plus the consumers around the path: --write-probs / --print-probs (Sample::write_probs,
 // src/Sample.cpp:63-85,154-186: streamed from the device in blocks of ECs), --write-likelihood / --read-likelihood /
-// --no-fit-model (include/Likelihood.hpp:224-273, src/mSWEEP.cpp:357-386), --run-rate (src/Sample.cpp:99-152,
+// --write-likelihood-bitseq / --no-fit-model (include/Likelihood.hpp:224-311, src/mSWEEP.cpp:357-386; the text of these
+// matrices is formatted on the device, msw_core_text_block, and only its bytes come to the host), --run-rate (src/Sample.cpp:99-152,
 // src/mSWEEP.cpp:524-548) and --bin-reads / --target-groups / --min-abundance (the mGEMS bins, src/mSWEEP.cpp:437-469:
 // the bin pass on the device, msw_core_bin_reads_aln; the driver's choices are those of msweep_amd/binning.py).  Same flags and messages as the reference for what it covers; held byte-for-byte against
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
@@ -44,6 +45,7 @@ struct Args {
   int gpu = 0;
   bool verbose = false;
   bool write_probs = false, print_probs = false, write_likelihood = false, no_fit_model = false, run_rate = false;
+  bool write_likelihood_bitseq = false;
   std::string read_likelihood;
   bool bin_reads = false, have_target_groups = false, have_min_abundance = false;
   std::vector<std::string> target_groups;
@@ -91,6 +93,7 @@ Args parse(int argc, char **argv) {
     else if (k == "--write-probs") a.write_probs = true;
     else if (k == "--print-probs") a.print_probs = true;
     else if (k == "--write-likelihood") a.write_likelihood = true;
+    else if (k == "--write-likelihood-bitseq") a.write_likelihood_bitseq = true;
     else if (k == "--read-likelihood") a.read_likelihood = val();
     else if (k == "--no-fit-model") a.no_fit_model = true;
     else if (k == "--run-rate") a.run_rate = true;
@@ -279,28 +282,128 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
   return 0;
 }
 
+// MSWEEP_HOST_TEXT=1 (developer switch): the matrices come to the host as doubles and are formatted here, cell by cell,
+// as before the device formatter -- the other side of its A/B and of tests/test_gpu_cli_text.py
+bool host_text() {
+  const char *e = getenv("MSWEEP_HOST_TEXT");
+  return e && e[0] == '1';
+}
+// classes per msw_core_text_block call: 8192, fewer when the worst-case text of a block (20 + cell * G + 2 n_zero + 12
+// bytes per line) would exceed 256 MiB; MSWEEP_TEXT_BLOCK=n (developer switch) overrides it
+size_t text_block_ecs(size_t n_groups, size_t n_zero, size_t cell) {
+  const char *e = getenv("MSWEEP_TEXT_BLOCK");
+  if (e && *e && std::strtoull(e, nullptr, 10) > 0) return (size_t)std::strtoull(e, nullptr, 10);
+  const size_t per_line = 20 + cell * n_groups + 2 * n_zero + 12;
+  return std::max<size_t>(1, std::min<size_t>(8192, ((size_t)256 << 20) / per_line));
+}
+
 // Sample::write_probs[2] (src/Sample.cpp:63-85,154-186): header `ec_id` + group names, one line per equivalence class
-// of exp(gamma); the G x E matrix is streamed from the device 8192 classes at a time (msw_core_gamma_block)
+// of exp(gamma).  The lines are formatted on the device a block of classes at a time (msw_core_text_block,
+// MSW_TEXT_PROBS); with MSWEEP_HOST_TEXT=1 the block comes as doubles (msw_core_gamma_block) and is formatted here.
 void write_probs(std::ostream &of, msw_handle h, const std::vector<std::string> &names, const std::vector<std::string> &zero_names,
                  size_t n_groups, size_t n_ecs) {
   of << "ec_id";
   for (auto &n : names) of << '\t' << n;
   for (auto &n : zero_names) of << '\t' << n;
   of << '\n';
-  const size_t block = 8192;
-  std::vector<double> buf(n_groups * block);
-  for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
-    const size_t w = std::min(block, n_ecs - e0);
-    check(h, msw_core_gamma_block(h, e0, e0 + w, buf.data(), w));
-    for (size_t jj = 0; jj < w; ++jj) {
-      of << e0 + jj;
-      for (size_t g = 0; g < n_groups; ++g) of << '\t' << g6(std::exp(buf[g * w + jj]));
-      for (size_t z = 0; z < zero_names.size(); ++z) of << "\t0";
-      of << '\n';
+  if (host_text()) {
+    const size_t block = 8192;
+    std::vector<double> buf(n_groups * block);
+    for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
+      const size_t w = std::min(block, n_ecs - e0);
+      check(h, msw_core_gamma_block(h, e0, e0 + w, buf.data(), w));
+      for (size_t jj = 0; jj < w; ++jj) {
+        of << e0 + jj;
+        for (size_t g = 0; g < n_groups; ++g) of << '\t' << g6(std::exp(buf[g * w + jj]));
+        for (size_t z = 0; z < zero_names.size(); ++z) of << "\t0";
+        of << '\n';
+      }
+    }
+  } else {
+    const size_t block = text_block_ecs(n_groups, zero_names.size(), 14);
+    for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
+      const char *text = nullptr;
+      size_t len = 0;
+      check(h, msw_core_text_block(h, MSW_TEXT_PROBS, e0, std::min(n_ecs, e0 + block), nullptr, zero_names.size(), &text, &len, nullptr));
+      of.write(text, (std::streamsize)len);
     }
   }
   of << '\n';
   of.flush();
+}
+
+// --write-likelihood (include/Likelihood.hpp:255-273): "count \t L(0,j) ... L(G-1,j)" per class, the lines formatted on
+// the device (MSW_TEXT_LOGL): no G x E matrix on the host.  MSWEEP_HOST_TEXT=1: the dense matrix, formatted here.
+void write_likelihood(std::ostream &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
+  if (host_text()) {
+    std::vector<double> L(n_kept * n_ecs);
+    check(h, msw_core_get_dense_logl(h, L.data(), n_ecs));
+    for (size_t j = 0; j < n_ecs; ++j) {
+      lf << ec_counts[j];
+      for (size_t g = 0; g < n_kept; ++g) lf << '\t' << g6(L[g * n_ecs + j]);
+      lf << '\n';
+    }
+    return;
+  }
+  const size_t block = text_block_ecs(n_kept, 0, 14);
+  for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
+    const char *text = nullptr;
+    size_t len = 0;
+    check(h, msw_core_text_block(h, MSW_TEXT_LOGL, e0, std::min(n_ecs, e0 + block), ec_counts.data() + e0, 0, &text, &len, nullptr));
+    lf.write(text, (std::streamsize)len);
+  }
+}
+
+// --write-likelihood-bitseq (include/Likelihood.hpp:275-311): five header lines, then one line per READ of every class --
+// the read id (from 1, never restarting) and the class's tail, which the device formats once per class
+// (MSW_TEXT_BITSEQ).  Ntotal / Nmap restate the reference's sum: std::accumulate starts from an `int` 0 with a lambda
+// that returns a double, so the total is truncated to an integer after every class, and exp(log c) can fall just below
+// c (a lone class of 5 reads gives 4): Ntotal can be below the number of reads.
+void write_likelihood_bitseq(std::ostream &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
+  long long total = 0;
+  for (uint64_t c : ec_counts) total = (long long)((double)total + std::exp(std::log((double)c)));
+  lf << "# Ntotal " << total << '\n' << "# Nmap " << total << '\n' << "# M " << n_kept << '\n'
+     << "# LOGFORMAT (probabilities saved on log scale.)" << '\n'
+     << "# r_name num_alignments (tr_id prob )^*{num_alignments}" << '\n';
+  uint64_t read_id = 1;
+  const bool on_host = host_text();
+  const size_t cell = 15 + std::to_string(n_kept + 1).size();
+  const size_t block = on_host ? 8192 : text_block_ecs(n_kept, 0, cell);
+  std::vector<double> buf;
+  std::string tails;
+  for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
+    const size_t w = std::min(block, n_ecs - e0);
+    const char *text = nullptr;
+    size_t len = 0;
+    if (on_host) {
+      // (the likelihood itself has no block entry on the host side: the dense matrix, once)
+      if (e0 == 0) {
+        buf.resize(n_kept * n_ecs);
+        check(h, msw_core_get_dense_logl(h, buf.data(), n_ecs));
+      }
+      tails.clear();
+      for (size_t j = e0; j < e0 + w; ++j) {
+        tails += std::to_string(n_kept + 1) + ' ';
+        for (size_t g = 0; g < n_kept; ++g) tails += std::to_string(g + 1) + ' ' + g6(buf[g * n_ecs + j]) + ' ';
+        tails += "0 -10000.00\n";
+      }
+      text = tails.data();
+      len = tails.size();
+    } else {
+      check(h, msw_core_text_block(h, MSW_TEXT_BITSEQ, e0, e0 + w, nullptr, 0, &text, &len, nullptr));
+    }
+    const char *p = text, *end = text + len;
+    for (size_t j = e0; j < e0 + w; ++j) {
+      const char *nl = (const char *)std::memchr(p, '\n', (size_t)(end - p));
+      if (!nl) throw std::runtime_error("the BitSeq text of a block ends before its last class");
+      for (uint64_t k = 0; k < ec_counts[j]; ++k) {
+        lf << read_id++ << ' ';
+        lf.write(p, (std::streamsize)(nl + 1 - p));
+      }
+      p = nl + 1;
+    }
+  }
+  lf.flush();
 }
 
 // digamma as the reference evaluates it (src/Sample.cpp:87-97)
@@ -418,19 +521,24 @@ int main(int argc, char **argv) {
       // (the likelihood is resident and the pseudoalignment could go -- but device memory given back is scrubbed before
       // it is handed out again, and the solver state is allocated next: it goes at the end)
     }
-    if (a.write_likelihood) {
-      // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
-      std::vector<double> L(n_kept * n_ecs);
-      check(h, msw_core_get_dense_logl(h, L.data(), n_ecs));
-      std::ofstream lf(a.prefix.empty() ? std::string("likelihoods.tsv") : a.prefix + "_likelihoods.tsv");
-      for (size_t j = 0; j < n_ecs; ++j) {
-        lf << ec_counts[j];
-        for (size_t g = 0; g < n_kept; ++g) lf << '\t' << g6(L[g * n_ecs + j]);
-        lf << '\n';
-      }
-    }
   } catch (const std::exception &ex) {
     std::cerr << "Building the log-likelihood array failed:\n  " << ex.what() << "\nexiting\n";
+    msw_core_destroy(h);
+    return 1;
+  }
+  try {
+    // written here if requested (src/mSWEEP.cpp:373-380: a failure has a message of its own)
+    if (a.write_likelihood_bitseq) {
+      // both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376)
+      std::ofstream lf(a.prefix.empty() ? std::string("bitseq_likelihoods.tsv") : a.prefix + "_bitseq_likelihoods.tsv");
+      write_likelihood_bitseq(lf, h, ec_counts, n_kept, n_ecs);
+    } else if (a.write_likelihood) {
+      // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
+      std::ofstream lf(a.prefix.empty() ? std::string("likelihoods.tsv") : a.prefix + "_likelihoods.tsv");
+      write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
+    }
+  } catch (const std::exception &ex) {
+    std::cerr << "Writing the likelihood to file failed:\n  " << ex.what() << "\nexiting\n";
     msw_core_destroy(h);
     return 1;
   }

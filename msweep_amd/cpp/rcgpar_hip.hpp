@@ -233,6 +233,26 @@ inline Gamma gamma_of(DeviceLikelihood &lik, size_t n_groups, size_t n_ecs) {
   return out;
 }
 
+// The lines of the classes [ec_begin, ec_end) of a matrix output, formatted on the device (msw_core_text_block):
+// MSW_TEXT_PROBS (Sample::write_probs, after a solve), MSW_TEXT_LOGL (Likelihood::write_likelihood_mSWEEP;
+// line_prefix = the read count of every class) or MSW_TEXT_BITSEQ (write_likelihood_BitSeq, the line after the read
+// id).  Written straight to `of`; returns the bytes written.
+inline size_t write_text_block(DeviceLikelihood &lik, int what, size_t ec_begin, size_t ec_end, std::ostream &of,
+                               const uint64_t *line_prefix = nullptr, size_t n_zero_cols = 0) {
+  const char *text = nullptr;
+  size_t len = 0;
+  check(lik.handle(), msw_core_text_block(lik.handle(), what, ec_begin, ec_end, line_prefix, n_zero_cols, &text, &len, nullptr));
+  of.write(text, (std::streamsize)len);
+  return len;
+}
+// printf("%g") of n doubles on the device, one per line (msw_core_format_g6: the formatter's diagnostic entry)
+inline std::string format_g6(DeviceLikelihood &lik, const double *x, size_t n) {
+  const char *text = nullptr;
+  size_t len = 0;
+  check(lik.handle(), msw_core_format_g6(lik.handle(), x, n, &text, &len, nullptr));
+  return std::string(text, len);
+}
+
 // ---- the likelihood of the unmodified call sites, kept across calls (file header) -------------------------------
 namespace detail {
 struct ShimCache {

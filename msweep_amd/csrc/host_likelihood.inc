@@ -574,6 +574,47 @@ GammaState gamma_state(Solver &s) {
   return GammaState{a, a >= 0.0 ? s.sc_host->tmax : s.sc_host->tmin, s.u.p};
 }
 
+// what a block of gamma (or of the likelihood itself: a = 1, u = 0) is computed from
+struct MaterialiseArgs {
+  double a = 1.0, tref = 0.0;
+  const double *u = nullptr;
+  DevBuf<double> zero_u;
+};
+void materialise_args(msw_core *h, bool gamma, MaterialiseArgs &m) {
+  const Resident &L = h->lik;
+  if (gamma) {
+    const GammaState gs = gamma_state(h->solver);
+    m.a = gs.a;
+    m.tref = gs.tref;
+    m.u = gs.u;
+  } else {
+    m.zero_u.alloc(L.G);
+    m.zero_u.zero(h->stream);
+    m.u = m.zero_u.p;
+  }
+  if (L.flavor == 0 && !h->iperm.p) {
+    h->iperm.alloc(L.E);
+    hipLaunchKernelGGL(k_invert_perm, dim3((L.E + 255) / 256), dim3(256), 0, h->stream, L.perm.p, L.E, h->iperm.p);
+  }
+}
+// the ECs [j0, j1) into device memory, buf[g * (j1 - j0) + (j - j0)]: enqueued on the handle's stream
+void materialise_block(msw_core *h, const MaterialiseArgs &m, bool gamma, size_t j0, size_t j1, double *buf) {
+  const Resident &L = h->lik;
+  const uint32_t G = L.G;
+  const size_t w = j1 - j0;
+  const unsigned nb = (unsigned)std::min<size_t>((w + 255) / 256, 4096);
+  if (L.flavor == 0) {
+    auto k = L.enc == kEncValue ? k_gamma_block<kEncValue>
+                                 : (L.wide() ? k_gamma_block<kEncWide> : (L.hybrid() ? k_gamma_block<kEncIndex> : k_gamma_block<kEncNarrow>));
+    hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, h->stream, sell_view(L, h->solver), h->iperm.p, (uint32_t)j0,
+                       (uint32_t)j1, m.a, L.logzi, m.tref, m.u, L.lut.p, gamma ? 1 : 0, buf, w);
+  } else {
+    hipLaunchKernelGGL(k_gamma_dense, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, L.Lt.p, (int)G,
+                       (uint32_t)w, m.a, m.u, gamma ? 1 : 0, buf, w, 0, (int)G, (uint32_t)j0);
+  }
+  MSW_HIP(hipGetLastError());
+}
+
 void materialise_impl(msw_core *h, double *out, size_t ld, bool gamma, size_t e0, size_t e1) {
   const Resident &L = h->lik;
   if (L.flavor < 0) throw Fail("no likelihood resident");
@@ -582,39 +623,14 @@ void materialise_impl(msw_core *h, double *out, size_t ld, bool gamma, size_t e0
   if (e0 > e1 || e1 > E) throw Fail("EC range out of bounds");
   if (ld < e1 - e0) throw Fail("ld smaller than the number of ECs asked for");
   if (e0 == e1) return;
-  double a = 1.0, tref = 0.0;
-  DevBuf<double> zero_u;
-  const double *u = nullptr;
-  if (gamma) {
-    const GammaState gs = gamma_state(h->solver);
-    a = gs.a;
-    tref = gs.tref;
-    u = gs.u;
-  } else {
-    zero_u.alloc(G);
-    zero_u.zero(h->stream);
-    u = zero_u.p;
-  }
-  if (L.flavor == 0 && !h->iperm.p) {
-    h->iperm.alloc(E);
-    hipLaunchKernelGGL(k_invert_perm, dim3((E + 255) / 256), dim3(256), 0, h->stream, L.perm.p, E, h->iperm.p);
-  }
+  MaterialiseArgs m;
+  materialise_args(h, gamma, m);
   const size_t blk = std::max<size_t>(1, std::min<size_t>(e1 - e0, ((size_t)1 << 27) / std::max<uint32_t>(G, 1)));
   DevBuf<double> buf;
   buf.alloc((size_t)G * blk);
   for (size_t j0 = e0; j0 < e1; j0 += blk) {
     const size_t j1 = std::min(e1, j0 + blk), w = j1 - j0;
-    const unsigned nb = (unsigned)std::min<size_t>((w + 255) / 256, 4096);
-    if (L.flavor == 0) {
-      auto k = L.enc == kEncValue ? k_gamma_block<kEncValue>
-                                   : (L.wide() ? k_gamma_block<kEncWide> : (L.hybrid() ? k_gamma_block<kEncIndex> : k_gamma_block<kEncNarrow>));
-      hipLaunchKernelGGL(k, dim3(nb), dim3(256), 0, h->stream, sell_view(L, h->solver), h->iperm.p, (uint32_t)j0,
-                         (uint32_t)j1, a, L.logzi, tref, u, L.lut.p, gamma ? 1 : 0, buf.p, w);
-    } else {
-      hipLaunchKernelGGL(k_gamma_dense, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, L.Lt.p, (int)G,
-                         (uint32_t)w, a, u, gamma ? 1 : 0, buf.p, w, 0, (int)G, (uint32_t)j0);
-    }
-    MSW_HIP(hipGetLastError());
+    materialise_block(h, m, gamma, j0, j1, buf.p);
     MSW_HIP(hipMemcpy2DAsync(out + (j0 - e0), ld * sizeof(double), buf.p, w * sizeof(double), w * sizeof(double), G,
                              hipMemcpyDeviceToHost, h->stream));
     MSW_HIP(hipStreamSynchronize(h->stream));

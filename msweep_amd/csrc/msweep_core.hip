@@ -36,6 +36,7 @@
 #include "stream_kernels.hpp"
 #include "reader_kernels.hpp"
 #include "bin_kernels.hpp"
+#include "text_kernels.hpp"
 
 using namespace msw;
 
@@ -177,6 +178,29 @@ struct Worker {  // a bootstrap worker: replicates on a stream of their own, bes
   ~Worker() { (void)hipStreamDestroy(s.stream); }
 };
 
+// ---- what msw_core_text_block / msw_core_format_g6 keep between calls (host_text.inc) ----------------------------
+struct TextState {
+  char *pinned = nullptr;  // the text handed to the caller, valid until the next call
+  size_t pinned_cap = 0;
+  DevBuf<double> val;      // the G x w block of values
+  DevBuf<uint8_t> out, tmp;
+  DevBuf<uint32_t> len, n_list;
+  DevBuf<uint64_t> off, prefix;
+  DevBuf<TextHostCell> list;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the length pass + scan, around the write pass
+  double kernel_ms = 0.0;  // of the last call (msw_core_last_text_timing)
+  uint64_t bytes = 0;
+  void release_device() {
+    val.release(); out.release(); tmp.release(); len.release(); n_list.release(); off.release(); prefix.release();
+    list.release();
+  }
+  ~TextState() {
+    if (pinned) (void)hipHostFree(pinned);
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -193,6 +217,7 @@ struct msw_core {
 
   Resident lik;
   DevBuf<uint32_t> iperm;  // original EC index -> permuted position (gamma blocks; built on first use)
+  TextState text;
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
   // ---- bootstrap -------------------------------------------------------------------------
@@ -986,6 +1011,7 @@ struct StageTimer {
 #include "host_alignment.inc"
 #include "host_reader.inc"
 #include "host_bin.inc"
+#include "host_text.inc"
 
 // =========================================================================================
 // C ABI
@@ -1090,6 +1116,7 @@ int msw_core_trim(msw_handle h) {
   return guarded(h, [&] {
     MSW_HIP(hipStreamSynchronize(h->stream));
     h->reader_pool.trim();
+    h->text.release_device();  // (the pinned text of the last msw_core_text_block stays valid)
   });
 }
 
@@ -1201,6 +1228,22 @@ int msw_core_gamma_block(msw_handle h, size_t ec_begin, size_t ec_end, double *g
   return guarded(h, [&] {
     if (!h->solver.have_solution) throw Fail("msw_core_gamma_block: no solve has run on this handle");
     materialise_impl(h, gamma_out, ld, /*gamma=*/true, ec_begin, ec_end);
+  });
+}
+
+int msw_core_text_block(msw_handle h, int what, size_t ec_begin, size_t ec_end, const uint64_t *line_prefix,
+                        size_t n_zero_cols, const char **text_out, size_t *len_out, size_t *n_host_cells_out) {
+  return guarded(h, [&] { text_block_impl(h, what, ec_begin, ec_end, line_prefix, n_zero_cols, text_out, len_out, n_host_cells_out); });
+}
+
+int msw_core_format_g6(msw_handle h, const double *x, size_t n, const char **text_out, size_t *len_out, size_t *n_host_out) {
+  return guarded(h, [&] { format_g6_impl(h, x, n, text_out, len_out, n_host_out); });
+}
+
+int msw_core_last_text_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out) {
+  return guarded(h, [&] {
+    if (kernel_ms_out) *kernel_ms_out = h->text.kernel_ms;
+    if (bytes_out) *bytes_out = h->text.bytes;
   });
 }
 
