@@ -245,6 +245,37 @@ int msw_core_format_g6(msw_handle h, const double *x, size_t n,
  * bytes are not in it -- and the bytes of text the kernels wrote (undecided cells still 13 blanks wide). */
 int msw_core_last_text_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out);
 
+/* --compress z / --compression-level (src/OutfileDesignator.cpp:30-37: the reference wraps its output files in a
+ * compressing stream on the host): the text outputs as ONE ordinary single-member gzip file (RFC 1952 / RFC 1951)
+ * whose DEFLATE stream is written on the device (deflate_kernels.hpp), where the text lies: only the compressed bytes
+ * cross the link.  One stream may be open per handle.  Every call returns bytes to APPEND to the file: *out points into a
+ * pinned host buffer owned by the handle, valid until the next call on the handle; *len_out may be 0.
+ * The text of every call is cut into chunks of 32 KiB that are compressed on their own (no match crosses a chunk or a
+ * call; each is one dynamic or stored block followed by an empty stored block, as pigz writes them), so the bytes are a
+ * function of the text, the chunk size and the call boundaries alone.  Level 0 writes stored blocks; levels 1 ... 9 run
+ * the SAME parse -- this core has one effort setting (greedy, single-entry hash buckets, dynamic codes).  The CRC-32 is
+ * computed on the device at every level.
+ * Calling append / text_block_gzip / end without an open stream, begin while one is open, or a level outside 0 ... 9 is
+ * refused (non-zero, msw_last_error); the handle stays usable.
+ * MSWEEP_HOST_GZIP=1 in the environment at begin (developer switch): the same calls bring the plain text to the host and
+ * compress it with zlib at the requested level -- the reference's method, the other side of the A/B and of the tests. */
+/* src/OutfileDesignator.cpp:30-37: opens the stream; returns the gzip header (mtime 0, OS 255). */
+int msw_core_gzip_begin(msw_handle h, int level, const char **out, size_t *len_out);
+/* src/OutfileDesignator.cpp:30-37 around the matrix writers: the arguments and the refusals of msw_core_text_block; returns
+ * the compressed chunks of that text, its undecided cells put in on the device (a block with more of them than the
+ * list holds: formatted by the host and uploaded).  *text_len_out (may be NULL): the uncompressed length. */
+int msw_core_text_block_gzip(msw_handle h, int what, size_t ec_begin, size_t ec_end,
+                             const uint64_t *line_prefix, size_t n_zero_cols,
+                             const char **out, size_t *len_out, size_t *n_host_cells_out, size_t *text_len_out);
+/* src/OutfileDesignator.cpp:30-37 around everything else the drivers write (header lines, the BitSeq lines per read, the
+ * bins): n host bytes, uploaded and compressed through the same kernels.  n == 0 is valid; at most 1 GiB a call. */
+int msw_core_gzip_append(msw_handle h, const char *bytes, size_t n, const char **out, size_t *len_out);
+/* src/OutfileDesignator.cpp:30-37, the stream's destructor: the final block, CRC-32 and ISIZE; closes the stream. */
+int msw_core_gzip_end(msw_handle h, const char **out, size_t *len_out);
+/* Measurement hook (tools/gzip_timing.py): device time of the gzip kernels (parse, CRC, scan, emit; events on the handle's
+ * stream) over the stream that is open or was closed last, the bytes of text it took and the bytes it returned. */
+int msw_core_last_gzip_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_in_out, uint64_t *bytes_out_out);
+
 /* Per-iteration diagnostics of the last solve (what rcgpar logs every 5th iteration to
  * the verbose stream, src/mSWEEP.cpp:198): arrays of length n (<= max recorded, 4096);
  * theta_trace is n x G or NULL.  Returns the number of iterations recorded via *n_out. */

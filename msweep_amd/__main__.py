@@ -3,7 +3,9 @@ over the MI355X core: Themisto plaintext in, `<prefix>_abundances.txt` out, and 
 mGEMS bins `<dir>/<group>.bin` (src/mSWEEP.cpp:437-469; the bin pass runs on the device, msweep_amd/binning.py
 holds the driver's side).  The matrix outputs -- --write-probs / --print-probs, --write-likelihood,
 --write-likelihood-bitseq -- are formatted on the device (Core.text_block): only their bytes come to the host.
-Compression of the outputs is out of scope."""
+--compress z (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62) writes them and the bins as `<name>.gz`, the
+gzip stream compressed on the device as well (Core.gzip_begin / text_block_gzip / gzip_append / gzip_end); bz2, lzma
+and zstd are refused, and --compression-level 1 ... 9 all run the core's one parse (0 stores)."""
 import argparse
 import math
 import os
@@ -49,6 +51,8 @@ def parse(argv):
     ap.add_argument("--bin-reads", action="store_true")
     ap.add_argument("--target-groups", type=lambda v: v.split(","))
     ap.add_argument("--min-abundance", type=float)
+    ap.add_argument("--compress", default="plaintext", help="plaintext or z (gzip, written on the device)")
+    ap.add_argument("--compression-level", type=int, default=6, help="0 stores; 1 ... 9 run the same parse")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
@@ -81,6 +85,66 @@ def text_block_ecs(n_groups, n_zero=0, cell=14):
     return max(1, min(8192, (256 << 20) // (20 + cell * n_groups + 2 * n_zero + 12)))
 
 
+class GzipOut:
+    """--compress z: `<path>.gz` (the extension is appended, as OutfileDesignator::open does, src/OutfileDesignator.cpp:30-62),
+    its bytes from the one gzip stream the handle holds open.  write takes host bytes (Core.gzip_append), text_block a
+    block of a matrix output (Core.text_block_gzip).  Both drivers make the same calls, so they write the same file."""
+    PIECE = 1 << 30     # host bytes per gzip_append call
+
+    def __init__(self, core, path, level):
+        self.core = core
+        head = core.gzip_begin(level)       # the stream first: a refusal leaves no file behind
+        self.open = True
+        try:
+            self.f = open(path + ".gz", "wb")
+        except OSError:
+            self.open = False
+            core.gzip_end()
+            raise
+        self.f.write(head)
+
+    def write(self, data):
+        """host bytes, or text (encoded), into the stream"""
+        if isinstance(data, str):
+            data = data.encode()
+        for o in range(0, len(data), self.PIECE):
+            self.f.write(self.core.gzip_append(data[o:o + self.PIECE]))
+
+    def text_block(self, what, e0, e1, **kw):
+        self.f.write(self.core.text_block_gzip(what, e0, e1, **kw))
+
+    def flush(self):
+        pass
+
+    def close(self):
+        if self.open:
+            self.open = False
+            self.f.write(self.core.gzip_end())
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            self.close()
+        except MswError:
+            if exc_type is None:
+                raise
+
+
+def _open_out(core, path, a, mode="wb"):
+    """an output file of the run: plain, or `<path>.gz` under --compress z"""
+    return GzipOut(core, path, a.compression_level) if a.compress == "z" else open(path, mode)
+
+
+def _text_block(f, core, what, e0, e1, **kw):
+    if isinstance(f, GzipOut):
+        f.text_block(what, e0, e1, **kw)
+    else:
+        f.write(core.text_block(what, e0, e1, **kw))
+
+
 def _bytes_out(f):
     """where bytes go on a text stream (files opened here are binary already)"""
     if hasattr(f, "buffer"):
@@ -94,14 +158,15 @@ def write_likelihood_file(f, ec_counts, lik):
     formatted on the device (TEXT_LOGL): no G x E matrix on the host.  MSWEEP_HOST_TEXT=1: the dense matrix, here."""
     if host_text():
         L = lik.log_mat()
-        for j in range(L.shape[1]):
-            f.write((str(int(ec_counts[j])) + "\t" + "\t".join("%g" % x for x in L[:, j]) + "\n").encode())
+        for e0 in range(0, L.shape[1], 8192):
+            f.write("".join(str(int(ec_counts[j])) + "\t" + "\t".join("%g" % x for x in L[:, j]) + "\n"
+                            for j in range(e0, min(L.shape[1], e0 + 8192))).encode())
         return
     E, block = lik.n_ecs, text_block_ecs(lik.n_groups)
     counts = np.asarray(ec_counts, np.uint64)
     for e0 in range(0, E, block):
         e1 = min(E, e0 + block)
-        f.write(lik.core.text_block(TEXT_LOGL, e0, e1, line_prefix=counts[e0:e1]))
+        _text_block(f, lik.core, TEXT_LOGL, e0, e1, line_prefix=counts[e0:e1])
 
 
 def bitseq_total(ec_counts):
@@ -135,28 +200,31 @@ def write_likelihood_bitseq(f, ec_counts, lik):
             tails = lik.core.text_block(TEXT_BITSEQ, e0, e1).split(b"\n")[:-1]
         if len(tails) != e1 - e0:
             raise RuntimeError("the BitSeq text of a block ends before its last class")
+        lines = []      # (one write per block: under --compress z a write is a call on the gzip stream)
         for j, tail in zip(range(e0, e1), tails):
             c = int(ec_counts[j])
-            f.write(b"".join(str(read_id + k).encode() + b" " + tail + b"\n" for k in range(c)))
+            lines.append(b"".join(str(read_id + k).encode() + b" " + tail + b"\n" for k in range(c)))
             read_id += c
+        f.write(b"".join(lines))
 
 
 def write_probs(of, names, zero_names, core, block=8192):
     """Sample::write_probs[2] (src/Sample.cpp:63-85,154-186), one line per EC.  The lines are formatted on the device a
     block of classes at a time (TEXT_PROBS); with MSWEEP_HOST_TEXT=1 the block comes as doubles (msw_core_gamma_block)
-    and is formatted here.  The G x E matrix is never held, here or there."""
+    and is formatted here.  The G x E matrix is never held, here or there.  `of`: a text stream, or a GzipOut."""
     of.write("ec_id\t" + "\t".join(list(names) + list(zero_names)) + "\n")
     G, E = core.shape()[:2]
     if host_text():
         for e0 in range(0, E, block):
             probs = np.exp(core.gamma_block(e0, min(E, e0 + block)))
-            for jj in range(probs.shape[1]):
-                of.write(str(e0 + jj) + "\t" + "\t".join(["%g" % x for x in probs[:, jj]] + ["0"] * len(zero_names)) + "\n")
+            # (one write per block: under --compress z a write is a call on the gzip stream)
+            of.write("".join(str(e0 + jj) + "\t" + "\t".join(["%g" % x for x in probs[:, jj]] + ["0"] * len(zero_names)) + "\n"
+                             for jj in range(probs.shape[1])))
     else:
         raw = _bytes_out(of)
         block = text_block_ecs(G, len(zero_names))
         for e0 in range(0, E, block):
-            raw.write(core.text_block(TEXT_PROBS, e0, min(E, e0 + block), n_zero_cols=len(zero_names)))
+            _text_block(raw, core, TEXT_PROBS, e0, min(E, e0 + block), n_zero_cols=len(zero_names))
         raw.flush()
     of.write("\n")
     of.flush()
@@ -201,8 +269,13 @@ def bin_reads(core, aln, estimated_names, theta, a):
         return 1
     for k, name in enumerate(targets):
         try:
-            binning.write_bin(binning.bin_path(a.prefix, name), reads[int(bin_ptr[k]):int(bin_ptr[k + 1])])
-        except OSError as ex:
+            ids = reads[int(bin_ptr[k]):int(bin_ptr[k + 1])]
+            if a.compress == "z":
+                with GzipOut(core, binning.bin_path(a.prefix, name), a.compression_level) as f:    # <dir>/<group>.bin.gz
+                    f.write(binning.format_ids(ids))
+            else:
+                binning.write_bin(binning.bin_path(a.prefix, name), ids)
+        except (OSError, MswError) as ex:
             sys.stderr.write(f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
             return 1
     return 0
@@ -211,6 +284,17 @@ def bin_reads(core, aln, estimated_names, theta, a):
 def main(argv=None):
     a = parse(sys.argv[1:] if argv is None else argv)
     aln = None
+    # before the GPU is touched: the reference's words (src/OutfileDesignator.cpp:30-62) for what this core does not build
+    if a.compress not in ("plaintext", "z"):
+        sys.stderr.write(f"Parsing arguments failed:\n  unsupported compression type {a.compress} "
+                         "(this core builds z only: gzip, compressed on the device)\nexiting\n")
+        return 1
+    if not 0 <= a.compression_level <= 9:
+        sys.stderr.write(f"Parsing arguments failed:\n  unsupported compression level {a.compression_level} "
+                         "(this core builds z only, levels 0 ... 9)\nexiting\n")
+        return 1
+    if not a.prefix:
+        a.compress = "plaintext"        # what goes to stdout stays plain
     if a.bin_reads and a.read_likelihood:
         # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
         sys.stderr.write("Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n")
@@ -264,12 +348,12 @@ def main(argv=None):
         if a.write_likelihood_bitseq:
             # both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376); <prefix>_bitseq_likelihoods.tsv
             # (src/OutfileDesignator.cpp:67-74)
-            with open(f"{a.prefix}_bitseq_likelihoods.tsv" if a.prefix else "bitseq_likelihoods.tsv", "wb") as f:
+            with _open_out(core, f"{a.prefix}_bitseq_likelihoods.tsv" if a.prefix else "bitseq_likelihoods.tsv", a) as f:
                 write_likelihood_bitseq(f, ec_counts, lik)
         elif a.write_likelihood:
             # --write-likelihood (include/Likelihood.hpp:255-273), default ostream precision; the file is
             # <prefix>_likelihoods.tsv (src/OutfileDesignator.cpp:67-74; the flag's help text says .txt)
-            with open(f"{a.prefix}_likelihoods.tsv" if a.prefix else "likelihoods.tsv", "wb") as f:
+            with _open_out(core, f"{a.prefix}_likelihoods.tsv" if a.prefix else "likelihoods.tsv", a) as f:
                 write_likelihood_file(f, ec_counts, lik)
     except (MswError, RuntimeError, OSError) as ex:
         sys.stderr.write(f"Writing the likelihood to file failed:\n  {ex}\nexiting\n")
@@ -325,7 +409,7 @@ def main(argv=None):
     zero = [n for n, m in zip(names, mask) if not m]
     if a.write_probs or a.print_probs:
         # Sample::write_probs (src/Sample.cpp:63-85): header ec_id + group names, one row per EC of exp(gamma)
-        for dst in ([open(f"{a.prefix}_probs.tsv", "w")] if a.write_probs and a.prefix else []) + \
+        for dst in ([_open_out(core, f"{a.prefix}_probs.tsv", a, "w")] if a.write_probs and a.prefix else []) + \
                    ([sys.stdout] if a.print_probs or (a.write_probs and not a.prefix) else []):
             write_probs(dst, est, zero if a.min_hits > 0 else [], core)
             if dst is not sys.stdout:

@@ -36,6 +36,7 @@ EXPORTS = [
     "msw_core_last_bootstrap_timing", "msw_core_layout_info", "msw_core_guarded_visits", "msw_core_set_pack_schedule",
     "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
+    "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
 ]
 
 
@@ -130,6 +131,11 @@ def load_library():
     L.msw_core_text_block.argtypes = [vp, C.c_int, sz, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.msw_core_format_g6.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.msw_core_last_text_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64)]
+    L.msw_core_gzip_begin.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    L.msw_core_text_block_gzip.argtypes = [vp, C.c_int, sz, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.msw_core_gzip_append.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.msw_core_gzip_end.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.msw_core_last_gzip_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.msw_core_trace.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.msw_core_set_trace_theta.argtypes = [vp, sz]
     L.msw_core_bootstrap.argtypes = [vp, vp, C.c_int32, sz, sz, sz, vp, dp, sz, C.c_int, C.c_int, vp, vp]
@@ -490,6 +496,46 @@ class Core:
         ms, nb = C.c_double(), C.c_uint64()
         self._check(self._L.msw_core_last_text_timing(self._h, C.byref(ms), C.byref(nb)))
         return ms.value, nb.value
+
+    # ---- --compress z: one gzip stream per handle, compressed on the device (msw_core_gzip_*).  Every call returns the
+    # bytes to append to the file -- a copy: the library's buffer lives until the next call only.
+    def gzip_begin(self, level=6):
+        """Opens the stream (level 0 ... 9; 0 stores, 1 ... 9 run the core's one parse); returns the gzip header."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.msw_core_gzip_begin(self._h, int(level), C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def text_block_gzip(self, what, ec_begin, ec_end, line_prefix=None, n_zero_cols=0, with_info=False):
+        """text_block into the open stream (msw_core_text_block_gzip): the compressed chunks of that text and, with_info,
+        (cells the host had to format, uncompressed length)."""
+        if line_prefix is not None:
+            line_prefix = _arr(line_prefix, np.uint64)
+            if len(line_prefix) != int(ec_end) - int(ec_begin):
+                raise MswError("text_block_gzip: one line_prefix per class of the range")
+        p, n, nh, nt = C.c_void_p(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._check(self._L.msw_core_text_block_gzip(self._h, int(what), int(ec_begin), int(ec_end), _ptr(line_prefix),
+                                                     int(n_zero_cols), C.byref(p), C.byref(n), C.byref(nh), C.byref(nt)))
+        out = C.string_at(p.value, n.value) if n.value else b""
+        return (out, nh.value, nt.value) if with_info else out
+
+    def gzip_append(self, data):
+        """Host bytes into the open stream (msw_core_gzip_append): uploaded, compressed by the same kernels."""
+        data = bytes(data)
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.msw_core_gzip_append(self._h, data if data else None, len(data), C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def gzip_end(self):
+        """The final block, CRC-32 and length; closes the stream (msw_core_gzip_end)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.msw_core_gzip_end(self._h, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def last_gzip_timing(self):
+        """(device ms of the gzip kernels, bytes of text in, bytes out) of the stream open now or closed last"""
+        ms, ni, no = C.c_double(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.msw_core_last_gzip_timing(self._h, C.byref(ms), C.byref(ni), C.byref(no)))
+        return ms.value, ni.value, no.value
 
     def bin_reads(self, ec_rptr, ec_reads, targets, thresholds, want_reads=True):
         """mGEMS read binning of the last solve on the device (msw_core_bin_reads): the reads of EC j go to bin k when

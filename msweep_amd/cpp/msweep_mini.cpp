@@ -9,7 +9,9 @@
 // --write-likelihood-bitseq / --no-fit-model (include/Likelihood.hpp:224-311, src/mSWEEP.cpp:357-386; the text of these
 // matrices is formatted on the device, msw_core_text_block, and only its bytes come to the host), --run-rate (src/Sample.cpp:99-152,
 // src/mSWEEP.cpp:524-548) and --bin-reads / --target-groups / --min-abundance (the mGEMS bins, src/mSWEEP.cpp:437-469:
-// the bin pass on the device, msw_core_bin_reads_aln; the driver's choices are those of msweep_amd/binning.py).  Same flags and messages as the reference for what it covers; held byte-for-byte against
+// the bin pass on the device, msw_core_bin_reads_aln; the driver's choices are those of msweep_amd/binning.py), and
+// --compress z / --compression-level (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62: the matrix outputs and the
+// bins as `<name>.gz`, the gzip stream compressed on the device, msw_core_gzip_*; bz2, lzma and zstd are refused).  Same flags and messages as the reference for what it covers; held byte-for-byte against
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
 //
 //   g++ -std=c++17 -O2 -o msweep_mini msweep_mini.cpp -L.. -lmsweep_core -Wl,-rpath,..
@@ -50,6 +52,8 @@ struct Args {
   bool bin_reads = false, have_target_groups = false, have_min_abundance = false;
   std::vector<std::string> target_groups;
   double min_abundance = 0.0;
+  std::string compress = "plaintext";  // or "z"
+  int compression_level = 6;           // 0 stores; 1 ... 9 run the core's one parse
 };
 
 std::vector<std::string> split(const std::string &s, char d) {
@@ -98,6 +102,8 @@ Args parse(int argc, char **argv) {
     else if (k == "--no-fit-model") a.no_fit_model = true;
     else if (k == "--run-rate") a.run_rate = true;
     else if (k == "--bin-reads") a.bin_reads = true;
+    else if (k == "--compress") a.compress = val();
+    else if (k == "--compression-level") a.compression_level = std::stoi(val());
     else if (k == "--target-groups") {
       a.target_groups = split(val(), ',');
       a.have_target_groups = true;
@@ -147,6 +153,73 @@ Grouping read_grouping(const std::string &path) {
 void check(msw_handle h, int rc) {
   if (rc != 0) throw std::runtime_error(msw_last_error(h));
 }
+
+// An output of the run: a stream that is there already (stdout), a plain file, or -- --compress z -- `<path>.gz`
+// (the extension is appended, as OutfileDesignator::open does, src/OutfileDesignator.cpp:30-62) whose bytes come from the
+// one gzip stream the handle holds open: write takes host bytes (msw_core_gzip_append), text_block a block of a matrix
+// output (msw_core_text_block_gzip).  The Python driver makes the same calls, so both write the same file.
+class Out {
+ public:
+  Out(msw_handle h, std::ostream &os) : h_(h), os_(&os) {}
+  Out(msw_handle h, const std::string &path, bool gz, int level) : h_(h), gz_(gz), os_(&file_) {
+    if (!gz_) {
+      file_.open(path);  // (a plain file that cannot be opened or written stays silent, as before --compress)
+      return;
+    }
+    // the stream first: a refusal leaves no file behind
+    const char *p = nullptr;
+    size_t n = 0;
+    check(h_, msw_core_gzip_begin(h_, level, &p, &n));
+    open_ = true;
+    file_.open(path + ".gz", std::ios::binary);
+    if (!file_) throw std::runtime_error("cannot open " + path + ".gz");  // (~Out closes the stream)
+    os_->write(p, (std::streamsize)n);
+  }
+  ~Out() {
+    if (!open_) return;
+    const char *p = nullptr;  // left open by a failure: the handle's stream is closed, the file is incomplete anyway
+    size_t n = 0;
+    (void)msw_core_gzip_end(h_, &p, &n);
+  }
+  void write(const char *p, size_t n) {
+    if (!gz_) {
+      os_->write(p, (std::streamsize)n);
+      return;
+    }
+    constexpr size_t kPiece = (size_t)1 << 30;  // host bytes per msw_core_gzip_append call
+    for (size_t o = 0; o < n; o += kPiece) {
+      const char *z = nullptr;
+      size_t nz = 0;
+      check(h_, msw_core_gzip_append(h_, p + o, std::min(kPiece, n - o), &z, &nz));
+      os_->write(z, (std::streamsize)nz);
+    }
+  }
+  void write(const std::string &s) { write(s.data(), s.size()); }
+  void text_block(int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero) {
+    const char *p = nullptr;
+    size_t n = 0;
+    if (gz_) check(h_, msw_core_text_block_gzip(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr, nullptr));
+    else check(h_, msw_core_text_block(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr));
+    os_->write(p, (std::streamsize)n);
+  }
+  void close() {
+    if (open_) {
+      open_ = false;
+      const char *p = nullptr;
+      size_t n = 0;
+      check(h_, msw_core_gzip_end(h_, &p, &n));
+      os_->write(p, (std::streamsize)n);
+    }
+    os_->flush();
+    if (gz_ && !*os_) throw std::runtime_error("writing the compressed file failed");
+  }
+
+ private:
+  msw_handle h_;
+  bool gz_ = false, open_ = false;
+  std::ofstream file_;
+  std::ostream *os_;
+};
 
 // a number as the reference's `*of << x` prints it (default ostream formatting: 6 significant digits)
 std::string g6(double x) {
@@ -267,6 +340,27 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
   }
   const size_t n = names.size(), nt = std::min(n, writer_threads());
   std::vector<std::string> err(n);
+  if (a.compress == "z") {
+    // <dir>/<group>.bin.gz, one gzip stream after the other: the handle holds one at a time
+    std::string ids;
+    char num[16];
+    for (size_t k = 0; k < n; ++k) {
+      try {
+        Out f(h, bin_path(a.prefix, names[k]), true, a.compression_level);
+        ids.clear();
+        for (uint64_t i = bin_ptr[k]; i < bin_ptr[k + 1]; ++i) {
+          ids.append(num, (size_t)(std::to_chars(num, num + sizeof num, reads[i]).ptr - num));
+          ids += '\n';
+        }
+        f.write(ids);
+        f.close();
+      } catch (const std::exception &ex) {
+        std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << ex.what() << "\nexiting\n";
+        return 1;
+      }
+    }
+    return 0;
+  }
   std::vector<std::thread> pool;
   for (size_t t = 0; t < nt; ++t)
     pool.emplace_back([&, t] {
@@ -300,58 +394,58 @@ size_t text_block_ecs(size_t n_groups, size_t n_zero, size_t cell) {
 // Sample::write_probs[2] (src/Sample.cpp:63-85,154-186): header `ec_id` + group names, one line per equivalence class
 // of exp(gamma).  The lines are formatted on the device a block of classes at a time (msw_core_text_block,
 // MSW_TEXT_PROBS); with MSWEEP_HOST_TEXT=1 the block comes as doubles (msw_core_gamma_block) and is formatted here.
-void write_probs(std::ostream &of, msw_handle h, const std::vector<std::string> &names, const std::vector<std::string> &zero_names,
+void write_probs(Out &of, msw_handle h, const std::vector<std::string> &names, const std::vector<std::string> &zero_names,
                  size_t n_groups, size_t n_ecs) {
-  of << "ec_id";
-  for (auto &n : names) of << '\t' << n;
-  for (auto &n : zero_names) of << '\t' << n;
-  of << '\n';
+  std::string head = "ec_id";
+  for (auto &n : names) head += '\t' + n;
+  for (auto &n : zero_names) head += '\t' + n;
+  of.write(head + '\n');
   if (host_text()) {
     const size_t block = 8192;
     std::vector<double> buf(n_groups * block);
+    std::string s;
     for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
       const size_t w = std::min(block, n_ecs - e0);
       check(h, msw_core_gamma_block(h, e0, e0 + w, buf.data(), w));
+      s.clear();
       for (size_t jj = 0; jj < w; ++jj) {
-        of << e0 + jj;
-        for (size_t g = 0; g < n_groups; ++g) of << '\t' << g6(std::exp(buf[g * w + jj]));
-        for (size_t z = 0; z < zero_names.size(); ++z) of << "\t0";
-        of << '\n';
+        s += std::to_string(e0 + jj);
+        for (size_t g = 0; g < n_groups; ++g) s += '\t' + g6(std::exp(buf[g * w + jj]));
+        for (size_t z = 0; z < zero_names.size(); ++z) s += "\t0";
+        s += '\n';
       }
+      of.write(s);  // (one write per block: under --compress z a write is a call on the gzip stream)
     }
   } else {
     const size_t block = text_block_ecs(n_groups, zero_names.size(), 14);
-    for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
-      const char *text = nullptr;
-      size_t len = 0;
-      check(h, msw_core_text_block(h, MSW_TEXT_PROBS, e0, std::min(n_ecs, e0 + block), nullptr, zero_names.size(), &text, &len, nullptr));
-      of.write(text, (std::streamsize)len);
-    }
+    for (size_t e0 = 0; e0 < n_ecs; e0 += block) of.text_block(MSW_TEXT_PROBS, e0, std::min(n_ecs, e0 + block), nullptr, zero_names.size());
   }
-  of << '\n';
-  of.flush();
+  of.write("\n", 1);
+  of.close();
 }
 
 // --write-likelihood (include/Likelihood.hpp:255-273): "count \t L(0,j) ... L(G-1,j)" per class, the lines formatted on
 // the device (MSW_TEXT_LOGL): no G x E matrix on the host.  MSWEEP_HOST_TEXT=1: the dense matrix, formatted here.
-void write_likelihood(std::ostream &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
+void write_likelihood(Out &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
   if (host_text()) {
     std::vector<double> L(n_kept * n_ecs);
     check(h, msw_core_get_dense_logl(h, L.data(), n_ecs));
-    for (size_t j = 0; j < n_ecs; ++j) {
-      lf << ec_counts[j];
-      for (size_t g = 0; g < n_kept; ++g) lf << '\t' << g6(L[g * n_ecs + j]);
-      lf << '\n';
+    std::string s;
+    for (size_t e0 = 0; e0 < n_ecs; e0 += 8192) {
+      s.clear();
+      for (size_t j = e0; j < std::min(n_ecs, e0 + 8192); ++j) {
+        s += std::to_string(ec_counts[j]);
+        for (size_t g = 0; g < n_kept; ++g) s += '\t' + g6(L[g * n_ecs + j]);
+        s += '\n';
+      }
+      lf.write(s);
     }
+    lf.close();
     return;
   }
   const size_t block = text_block_ecs(n_kept, 0, 14);
-  for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
-    const char *text = nullptr;
-    size_t len = 0;
-    check(h, msw_core_text_block(h, MSW_TEXT_LOGL, e0, std::min(n_ecs, e0 + block), ec_counts.data() + e0, 0, &text, &len, nullptr));
-    lf.write(text, (std::streamsize)len);
-  }
+  for (size_t e0 = 0; e0 < n_ecs; e0 += block) lf.text_block(MSW_TEXT_LOGL, e0, std::min(n_ecs, e0 + block), ec_counts.data() + e0, 0);
+  lf.close();
 }
 
 // --write-likelihood-bitseq (include/Likelihood.hpp:275-311): five header lines, then one line per READ of every class --
@@ -359,18 +453,17 @@ void write_likelihood(std::ostream &lf, msw_handle h, const std::vector<uint64_t
 // (MSW_TEXT_BITSEQ).  Ntotal / Nmap restate the reference's sum: std::accumulate starts from an `int` 0 with a lambda
 // that returns a double, so the total is truncated to an integer after every class, and exp(log c) can fall just below
 // c (a lone class of 5 reads gives 4): Ntotal can be below the number of reads.
-void write_likelihood_bitseq(std::ostream &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
+void write_likelihood_bitseq(Out &lf, msw_handle h, const std::vector<uint64_t> &ec_counts, size_t n_kept, size_t n_ecs) {
   long long total = 0;
   for (uint64_t c : ec_counts) total = (long long)((double)total + std::exp(std::log((double)c)));
-  lf << "# Ntotal " << total << '\n' << "# Nmap " << total << '\n' << "# M " << n_kept << '\n'
-     << "# LOGFORMAT (probabilities saved on log scale.)" << '\n'
-     << "# r_name num_alignments (tr_id prob )^*{num_alignments}" << '\n';
+  lf.write("# Ntotal " + std::to_string(total) + "\n# Nmap " + std::to_string(total) + "\n# M " + std::to_string(n_kept) +
+           "\n# LOGFORMAT (probabilities saved on log scale.)\n# r_name num_alignments (tr_id prob )^*{num_alignments}\n");
   uint64_t read_id = 1;
   const bool on_host = host_text();
   const size_t cell = 15 + std::to_string(n_kept + 1).size();
   const size_t block = on_host ? 8192 : text_block_ecs(n_kept, 0, cell);
   std::vector<double> buf;
-  std::string tails;
+  std::string tails, lines;
   for (size_t e0 = 0; e0 < n_ecs; e0 += block) {
     const size_t w = std::min(block, n_ecs - e0);
     const char *text = nullptr;
@@ -393,17 +486,20 @@ void write_likelihood_bitseq(std::ostream &lf, msw_handle h, const std::vector<u
       check(h, msw_core_text_block(h, MSW_TEXT_BITSEQ, e0, e0 + w, nullptr, 0, &text, &len, nullptr));
     }
     const char *p = text, *end = text + len;
+    lines.clear();  // (one write per block: under --compress z a write is a call on the gzip stream)
     for (size_t j = e0; j < e0 + w; ++j) {
       const char *nl = (const char *)std::memchr(p, '\n', (size_t)(end - p));
       if (!nl) throw std::runtime_error("the BitSeq text of a block ends before its last class");
       for (uint64_t k = 0; k < ec_counts[j]; ++k) {
-        lf << read_id++ << ' ';
-        lf.write(p, (std::streamsize)(nl + 1 - p));
+        lines += std::to_string(read_id++);
+        lines += ' ';
+        lines.append(p, (size_t)(nl + 1 - p));
       }
       p = nl + 1;
     }
+    lf.write(lines);
   }
-  lf.flush();
+  lf.close();
 }
 
 // digamma as the reference evaluates it (src/Sample.cpp:87-97)
@@ -451,6 +547,18 @@ int main(int argc, char **argv) {
     std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
+  // before the GPU is touched: the reference's words (src/OutfileDesignator.cpp:30-62) for what this core does not build
+  if (a.compress != "plaintext" && a.compress != "z") {
+    std::cerr << "Parsing arguments failed:\n  unsupported compression type " << a.compress
+              << " (this core builds z only: gzip, compressed on the device)\nexiting\n";
+    return 1;
+  }
+  if (a.compression_level < 0 || a.compression_level > 9) {
+    std::cerr << "Parsing arguments failed:\n  unsupported compression level " << a.compression_level
+              << " (this core builds z only, levels 0 ... 9)\nexiting\n";
+    return 1;
+  }
+  if (a.prefix.empty()) a.compress = "plaintext";  // what goes to stdout stays plain
   if (a.bin_reads && !a.read_likelihood.empty()) {
     // "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
     std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
@@ -530,11 +638,12 @@ int main(int argc, char **argv) {
     // written here if requested (src/mSWEEP.cpp:373-380: a failure has a message of its own)
     if (a.write_likelihood_bitseq) {
       // both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376)
-      std::ofstream lf(a.prefix.empty() ? std::string("bitseq_likelihoods.tsv") : a.prefix + "_bitseq_likelihoods.tsv");
+      Out lf(h, a.prefix.empty() ? std::string("bitseq_likelihoods.tsv") : a.prefix + "_bitseq_likelihoods.tsv", a.compress == "z",
+             a.compression_level);
       write_likelihood_bitseq(lf, h, ec_counts, n_kept, n_ecs);
     } else if (a.write_likelihood) {
       // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
-      std::ofstream lf(a.prefix.empty() ? std::string("likelihoods.tsv") : a.prefix + "_likelihoods.tsv");
+      Out lf(h, a.prefix.empty() ? std::string("likelihoods.tsv") : a.prefix + "_likelihoods.tsv", a.compress == "z", a.compression_level);
       write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
     }
   } catch (const std::exception &ex) {
@@ -612,10 +721,13 @@ int main(int argc, char **argv) {
       const std::vector<std::string> none;
       const std::vector<std::string> &zn = a.min_hits > 0 ? zero_names : none;
       if (a.write_probs && !a.prefix.empty()) {
-        std::ofstream pf(a.prefix + "_probs.tsv");
+        Out pf(h, a.prefix + "_probs.tsv", a.compress == "z", a.compression_level);
         write_probs(pf, h, est_names, zn, n_kept, n_ecs);
       }
-      if (a.print_probs || (a.write_probs && a.prefix.empty())) write_probs(std::cout, h, est_names, zn, n_kept, n_ecs);
+      if (a.print_probs || (a.write_probs && a.prefix.empty())) {
+        Out so(h, std::cout);
+        write_probs(so, h, est_names, zn, n_kept, n_ecs);
+      }
     }
   } catch (const std::exception &ex) {
     std::cerr << "Estimating relative abundances failed:\n  " << ex.what() << "\nexiting\n";

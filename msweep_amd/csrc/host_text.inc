@@ -77,10 +77,10 @@ void text_launch_what(msw_core *h, int what, const TextJob &J, TextState &T, uin
   else text_launch<kTextPlain>(h, J, T, cap, write);
 }
 
-// The text of the w lines whose values lie in T.val (G x w, group-major) appended to the pinned buffer at `used`;
-// returns the bytes appended.  prefix: host pointer (LOGL) or null.
-size_t text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
-                      size_t used, size_t &n_host) {
+// The text of the w lines whose values lie in T.val (G x w, group-major) into T.out: length pass, scan, write pass (left
+// enqueued).  Returns its length, undecided cells still 13 blanks wide.  prefix: host pointer (LOGL) or null.
+uint64_t text_block_device(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
+                           uint32_t cap) {
   TextState &T = h->text;
   hipStream_t st = h->stream;
   TextJob J{T.val.p, G, (uint32_t)w, id0, nullptr, (uint32_t)n_zero};
@@ -88,7 +88,6 @@ size_t text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0,
     T.prefix.upload(prefix, w, st);
     J.prefix = T.prefix.p;
   }
-  const uint32_t cap = text_list_cap();
   T.len.alloc(w + 1);
   T.off.alloc(w + 1);
   T.n_list.alloc(1);
@@ -109,37 +108,57 @@ size_t text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0,
   MSW_HIP(hipMemcpyAsync(&total, T.off.p + w, sizeof total, hipMemcpyDeviceToHost, st));
   MSW_HIP(hipStreamSynchronize(st));
   T.out.alloc((total + 3) & ~(uint64_t)3);
-  text_pinned_reserve(T, used + total, used);
   MSW_HIP(hipEventRecord(T.ev[2], st));
   text_launch_what(h, what, J, T, cap, true);
   MSW_HIP(hipEventRecord(T.ev[3], st));
-  uint32_t n_list = 0;
-  MSW_HIP(hipMemcpyAsync(&n_list, T.n_list.p, sizeof n_list, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipMemcpyAsync(T.pinned + used, T.out.p, total, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipStreamSynchronize(st));
+  return total;
+}
+// (after the stream has been synchronised behind text_block_device)
+void text_add_timing(TextState &T, uint64_t total) {
   float ms_len = 0.f, ms_write = 0.f;
   MSW_HIP(hipEventElapsedTime(&ms_len, T.ev[0], T.ev[1]));
   MSW_HIP(hipEventElapsedTime(&ms_write, T.ev[2], T.ev[3]));
   T.kernel_ms += (double)ms_len + (double)ms_write;
   T.bytes += total;
+}
+// PROBS on a block the host formats itself: the values the device formats, on the host
+void text_block_values(msw_core *h, int what, uint32_t G, size_t w, std::vector<double> &val) {
+  TextState &T = h->text;
+  const size_t n = (size_t)G * w;
+  if (what == kTextProbs) {
+    hipLaunchKernelGGL(k_text_exp, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, h->stream, T.val.p, n);
+    MSW_HIP(hipGetLastError());
+  }
+  val.resize(n);
+  MSW_HIP(hipMemcpyAsync(val.data(), T.val.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  MSW_HIP(hipStreamSynchronize(h->stream));
+}
+
+// The same text appended to the pinned buffer at `used`, the undecided cells filled in; returns the bytes appended.
+size_t text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
+                      size_t used, size_t &n_host) {
+  TextState &T = h->text;
+  hipStream_t st = h->stream;
+  const uint32_t cap = text_list_cap();
+  const uint64_t total = text_block_device(h, what, G, w, id0, prefix, n_zero, cap);
+  text_pinned_reserve(T, used + total, used);
+  uint32_t n_list = 0;
+  MSW_HIP(hipMemcpyAsync(&n_list, T.n_list.p, sizeof n_list, hipMemcpyDeviceToHost, st));
+  MSW_HIP(hipMemcpyAsync(T.pinned + used, T.out.p, total, hipMemcpyDeviceToHost, st));
+  MSW_HIP(hipStreamSynchronize(st));
+  text_add_timing(T, total);
   if (n_list == 0) return total;
   char *text = T.pinned + used;
   if (n_list > cap) {
     // more undecided cells than the list holds: the host formats this block from the values the device formatted
-    const size_t n = (size_t)G * w;
-    if (what == kTextProbs) {
-      hipLaunchKernelGGL(k_text_exp, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, st, T.val.p, n);
-      MSW_HIP(hipGetLastError());
-    }
-    std::vector<double> val(n);
-    MSW_HIP(hipMemcpyAsync(val.data(), T.val.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    MSW_HIP(hipStreamSynchronize(st));
+    std::vector<double> val;
+    text_block_values(h, what, G, w, val);
     std::string s;
     s.reserve(total);
     text_render_host(what, val, G, w, id0, prefix, n_zero, s);
     if (s.size() > total) throw Fail("msw_core_text_block: the host's text of a block is longer than the device's");
     std::memcpy(text, s.data(), s.size());
-    n_host += n;
+    n_host += (size_t)G * w;
     return s.size();
   }
   // the undecided cells in text order: print each into its 13 blanks and move what follows up against it
@@ -172,10 +191,9 @@ void text_return(msw_core *h, size_t used, size_t n_host, const char **text_out,
   if (n_host_out) *n_host_out = n_host;
 }
 
-void text_block_impl(msw_core *h, int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero,
-                     const char **text_out, size_t *len_out, size_t *n_host_out) {
+// the refusals of msw_core_text_block
+void text_block_check(msw_core *h, int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero) {
   const Resident &L = h->lik;
-  if (!text_out || !len_out) throw Fail("msw_core_text_block: null text_out or len_out");
   if (what != MSW_TEXT_PROBS && what != MSW_TEXT_LOGL && what != MSW_TEXT_BITSEQ)
     throw Fail("msw_core_text_block: unknown kind of text " + std::to_string(what));
   if (L.flavor < 0) throw Fail("msw_core_text_block: no likelihood resident");
@@ -195,21 +213,35 @@ void text_block_impl(msw_core *h, int what, size_t e0, size_t e1, const uint64_t
                std::to_string(fit) + " classes of " + std::to_string(G) + " groups and " + std::to_string(n_zero) +
                " zero columns fit one call");
   }
-  size_t used = 0, n_host = 0;
+}
+
+// run(G, w, j0, prefix of the block): once per block of classes of [e0, e1), its values materialised in T.val
+template <class F>
+void text_block_each(msw_core *h, int what, size_t e0, size_t e1, const uint64_t *prefix, F &&run) {
   h->text.kernel_ms = 0.0;
   h->text.bytes = 0;
-  if (e0 < e1) {
-    const bool gamma = what == MSW_TEXT_PROBS;
-    MaterialiseArgs m;
-    materialise_args(h, gamma, m);
-    const size_t blk = std::max<size_t>(1, std::min<size_t>(e1 - e0, ((size_t)1 << 27) / std::max<uint32_t>(G, 1)));
-    h->text.val.alloc((size_t)G * blk);
-    for (size_t j0 = e0; j0 < e1; j0 += blk) {
-      const size_t j1 = std::min(e1, j0 + blk);
-      materialise_block(h, m, gamma, j0, j1, h->text.val.p);
-      used += text_block_run(h, what, G, j1 - j0, j0, prefix ? prefix + (j0 - e0) : nullptr, n_zero, used, n_host);
-    }
+  if (e0 >= e1) return;
+  const uint32_t G = h->lik.G;
+  const bool gamma = what == MSW_TEXT_PROBS;
+  MaterialiseArgs m;
+  materialise_args(h, gamma, m);
+  const size_t blk = std::max<size_t>(1, std::min<size_t>(e1 - e0, ((size_t)1 << 27) / std::max<uint32_t>(G, 1)));
+  h->text.val.alloc((size_t)G * blk);
+  for (size_t j0 = e0; j0 < e1; j0 += blk) {
+    const size_t j1 = std::min(e1, j0 + blk);
+    materialise_block(h, m, gamma, j0, j1, h->text.val.p);
+    run(G, j1 - j0, j0, prefix ? prefix + (j0 - e0) : nullptr);
   }
+}
+
+void text_block_impl(msw_core *h, int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero,
+                     const char **text_out, size_t *len_out, size_t *n_host_out) {
+  if (!text_out || !len_out) throw Fail("msw_core_text_block: null text_out or len_out");
+  text_block_check(h, what, e0, e1, prefix, n_zero);
+  size_t used = 0, n_host = 0;
+  text_block_each(h, what, e0, e1, prefix, [&](uint32_t G, size_t w, size_t j0, const uint64_t *pre) {
+    used += text_block_run(h, what, G, w, j0, pre, n_zero, used, n_host);
+  });
   text_return(h, used, n_host, text_out, len_out, n_host_out);
 }
 

@@ -18,6 +18,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include <zlib.h>
+
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -37,6 +39,7 @@
 #include "reader_kernels.hpp"
 #include "bin_kernels.hpp"
 #include "text_kernels.hpp"
+#include "deflate_kernels.hpp"
 
 using namespace msw;
 
@@ -201,6 +204,36 @@ struct TextState {
   }
 };
 
+// ---- the gzip stream open on the handle and what its calls keep between them (host_gzip.inc) ---------------------------
+struct GzState {
+  bool open = false, host = false;  // host: MSWEEP_HOST_GZIP=1, zlib on the plain text
+  int level = 6;
+  uint32_t crc_reg = 0;  // the CRC register over the text so far (deflate_format.hpp: R(~0, text))
+  uint64_t isize = 0;    // ... and its length
+  std::unique_ptr<z_stream> zs;
+  char *pinned = nullptr;  // the compressed bytes handed to the caller, valid until the next call
+  size_t pinned_cap = 0;
+  DevBuf<uint8_t> in, closed, out, tmp;  // uploaded host bytes; a text block with its undecided cells closed; the chunks
+  DevBuf<uint32_t> tokens, tables, len, crc, pow8;
+  DevBuf<GzChunk> meta;
+  DevBuf<uint64_t> off;
+  DevBuf<GzCell> cells;
+  uint32_t pow8_host[40] = {};
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around parse + CRC + scan, around the emit pass
+  double kernel_ms = 0.0;  // of the stream (msw_core_last_gzip_timing)
+  uint64_t bytes_out = 0;
+  void release_device() {
+    in.release(); closed.release(); out.release(); tmp.release(); tokens.release(); tables.release(); len.release();
+    meta.release(); off.release(); cells.release();
+  }
+  ~GzState() {
+    if (zs) (void)deflateEnd(zs.get());
+    if (pinned) (void)hipHostFree(pinned);
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -218,6 +251,7 @@ struct msw_core {
   Resident lik;
   DevBuf<uint32_t> iperm;  // original EC index -> permuted position (gamma blocks; built on first use)
   TextState text;
+  GzState gz;
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
   // ---- bootstrap -------------------------------------------------------------------------
@@ -1012,6 +1046,7 @@ struct StageTimer {
 #include "host_reader.inc"
 #include "host_bin.inc"
 #include "host_text.inc"
+#include "host_gzip.inc"
 
 // =========================================================================================
 // C ABI
@@ -1117,6 +1152,7 @@ int msw_core_trim(msw_handle h) {
     MSW_HIP(hipStreamSynchronize(h->stream));
     h->reader_pool.trim();
     h->text.release_device();  // (the pinned text of the last msw_core_text_block stays valid)
+    h->gz.release_device();
   });
 }
 
@@ -1238,6 +1274,32 @@ int msw_core_text_block(msw_handle h, int what, size_t ec_begin, size_t ec_end, 
 
 int msw_core_format_g6(msw_handle h, const double *x, size_t n, const char **text_out, size_t *len_out, size_t *n_host_out) {
   return guarded(h, [&] { format_g6_impl(h, x, n, text_out, len_out, n_host_out); });
+}
+
+// ---- --compress z (src/OutfileDesignator.cpp:30-37) -----------------------------------------------------------------------
+int msw_core_gzip_begin(msw_handle h, int level, const char **out, size_t *len_out) {
+  return guarded(h, [&] { gzip_begin_impl(h, level, out, len_out); });
+}
+
+int msw_core_text_block_gzip(msw_handle h, int what, size_t ec_begin, size_t ec_end, const uint64_t *line_prefix, size_t n_zero_cols,
+                             const char **out, size_t *len_out, size_t *n_host_cells_out, size_t *text_len_out) {
+  return guarded(h, [&] { text_block_gzip_impl(h, what, ec_begin, ec_end, line_prefix, n_zero_cols, out, len_out, n_host_cells_out, text_len_out); });
+}
+
+int msw_core_gzip_append(msw_handle h, const char *bytes, size_t n, const char **out, size_t *len_out) {
+  return guarded(h, [&] { gzip_append_impl(h, bytes, n, out, len_out); });
+}
+
+int msw_core_gzip_end(msw_handle h, const char **out, size_t *len_out) {
+  return guarded(h, [&] { gzip_end_impl(h, out, len_out); });
+}
+
+int msw_core_last_gzip_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_in_out, uint64_t *bytes_out_out) {
+  return guarded(h, [&] {
+    if (kernel_ms_out) *kernel_ms_out = h->gz.kernel_ms;
+    if (bytes_in_out) *bytes_in_out = h->gz.isize;
+    if (bytes_out_out) *bytes_out_out = h->gz.bytes_out;
+  });
 }
 
 int msw_core_last_text_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out) {
