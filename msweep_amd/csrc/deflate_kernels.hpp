@@ -1,6 +1,6 @@
 // deflate_kernels.hpp -- gzip on the device (msw_core_gzip_* / msw_core_text_block_gzip, host_gzip.inc): with
-// --compress z the file's bytes are the compressed ones, so the compressor runs where the text lies and only its output
-// crosses the link.  Format, framing and the arithmetic shared with the host: deflate_format.hpp.
+// --compress z the file's bytes are the compressed ones, so the compressor runs where the text lies (a block's finished
+// text, text_kernels.hpp, or uploaded host bytes) and only its output crosses the link.  Format, framing and the arithmetic shared with the host: deflate_format.hpp.
 //
 // The text is cut into chunks of 32 KiB that are compressed independently, a wavefront each (wave64: __ballot is 64 bits
 // wide), in the text kernels' length pass / scan / write pass:
@@ -17,8 +17,6 @@
 //               leaves as whole dwords (text_flush).
 //   k_gz_crc    CRC-32 of the text: the register value of every 256-byte piece from a zero state, multiplied by
 //               x^(8 n) mod P for the n bytes behind it, all XORed together.
-//   k_text_close  the undecided cells of a text block (text_kernels.hpp) printed by the host, put in on the device:
-//               every stretch between them moves down by the slack accumulated in front of it.
 // The compressed bytes are a function of the text, the chunk size and the call boundaries alone.  No kernel uses
 // scratch memory; the parse holds 51 KiB of LDS (three workgroups a CU), the emit pass 34 KiB
 // (tests/test_deflate_kernel_resources.py).
@@ -38,12 +36,6 @@ static_assert(defl::build_lengths_ws(defl::kNumLit) <= (1u << defl::kHashBits), 
 
 struct GzChunk {  // what the parse leaves for the emit pass
   uint32_t n_tok, stored;
-};
-
-struct GzCell {  // an undecided cell as the host printed it: where its 13 blanks start, the slack in front of it
-  uint64_t off;
-  uint32_t slack, len;
-  char s[16];
 };
 
 // LDS image of a chunk: dwords, the text little-endian in them
@@ -263,30 +255,6 @@ __global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text
   }
   for (int d = 1; d < kWave; d <<= 1) acc ^= __shfl_xor(acc, d);
   if (threadIdx.x % kWave == 0 && acc) atomicXor(result, acc);
-}
-
-// dst <- src[0 .. total) with every listed cell's 13 blanks replaced by its text; cells sorted by offset
-__global__ __launch_bounds__(256) void k_text_close(const uint8_t *__restrict__ src, uint64_t total, const GzCell *__restrict__ cells,
-                                                    uint32_t n_cells, uint8_t *__restrict__ dst) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t lo = 0, hi = n_cells;  // lo <- the cells that start at or before byte i
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) / 2;
-      if (cells[mid].off <= i) lo = mid + 1;
-      else hi = mid;
-    }
-    uint64_t slack = 0;
-    if (lo) {
-      const GzCell *c = &cells[lo - 1];
-      const uint64_t j = i - c->off;
-      if (j < (uint64_t)g6::kMaxLen) {
-        if (j < c->len) dst[c->off - c->slack + j] = (uint8_t)c->s[j];
-        continue;
-      }
-      slack = (uint64_t)c->slack + ((uint32_t)g6::kMaxLen - c->len);
-    }
-    dst[i - slack] = src[i];
-  }
 }
 
 }  // namespace msw

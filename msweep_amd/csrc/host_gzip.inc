@@ -1,38 +1,24 @@
 // host_gzip.inc -- msw_core_gzip_* / msw_core_text_block_gzip (included by msweep_core.hip): --compress z, the gzip
 // stream of a text output compressed on the device (deflate_kernels.hpp).  One stream may be open per handle; every call
 // returns the bytes to append to the file in the handle's pinned buffer.  Per call: the text where it lies (a text block:
-// the text kernels' output, undecided cells closed on the device; host bytes: uploaded), the parse and the CRC, an
-// exclusive scan of the chunks' byte lengths, the emit pass, one copy of the compressed bytes.  Device memory beside the
-// text: 4 bytes of token scratch per byte of text, the compressed bytes, O(chunks) tables; nothing of that size goes to
-// the host.  The handle keeps the running CRC register and length: a call's CRC value joins them with one
-// multiplication by x^(8 n) on the host.
+// its finished text, text_block_finish of host_text.inc, whose other sink this file is; host bytes: uploaded), the parse
+// and the CRC, an exclusive scan of the chunks' byte lengths, the emit pass, one copy of the compressed bytes.  Device
+// memory beside the text: 4 bytes of token scratch per byte of text, the compressed bytes, O(chunks) tables; nothing of
+// that size goes to the host.  The handle keeps the running CRC register and length: a call's CRC value joins them with
+// one multiplication by x^(8 n) on the host.
 // MSWEEP_HOST_GZIP=1 (developer switch, read at begin): the same calls bring the plain text to the host and compress it
 // with zlib at the requested level -- the reference's method (src/OutfileDesignator.cpp:30-37), the other side of the A/B.
 namespace {
 
 constexpr size_t kGzMaxBytes = (size_t)1 << 30;  // host bytes of one append
 
-void gz_pinned_reserve(GzState &Z, size_t need, size_t used) {
-  if (need <= Z.pinned_cap) return;
-  const size_t cap = std::max(need, Z.pinned_cap + Z.pinned_cap / 2);
-  char *p = nullptr;
-  if (hipHostMalloc((void **)&p, cap, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    throw Fail("msw_core_gzip: cannot allocate " + std::to_string(cap) + " bytes of pinned host memory for the compressed bytes");
-  }
-  if (used) std::memcpy(p, Z.pinned, used);
-  if (Z.pinned) (void)hipHostFree(Z.pinned);
-  Z.pinned = p;
-  Z.pinned_cap = cap;
-}
-
 void gz_require_open(msw_core *h, const char *who) {
   if (!h->gz.open) throw Fail(std::string(who) + ": no gzip stream is open on this handle (msw_core_gzip_begin)");
 }
 
 void gz_return(msw_core *h, size_t used, const char **out, size_t *len) {
-  gz_pinned_reserve(h->gz, 1, 0);  // an empty result still points somewhere
-  *out = h->gz.pinned;
+  pinned_reserve(h->gz.pinned, 1, 0);  // an empty result still points somewhere
+  *out = h->gz.pinned.p;
   *len = used;
   h->gz.bytes_out += used;
 }
@@ -63,18 +49,10 @@ size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) 
   hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((pieces + 255) / 256, (size_t)h->n_cu * 32))),
                      dim3(256), 0, st, d, (uint64_t)n, Z.pow8.p, Z.crc.p);
   MSW_HIP(hipGetLastError());
-  auto len64 = rocprim::make_transform_iterator(Z.len.p, U32ToU64{});
-  size_t tmp_bytes = 0;
-  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, Z.off.p, (uint64_t)0, nch + 1, rocprim::plus<uint64_t>(), st));
-  Z.tmp.alloc(tmp_bytes);
-  MSW_HIP(rocprim::exclusive_scan(Z.tmp.p, tmp_bytes, len64, Z.off.p, (uint64_t)0, nch + 1, rocprim::plus<uint64_t>(), st));
-  MSW_HIP(hipEventRecord(Z.ev[1], st));
-  uint64_t total = 0;
-  MSW_HIP(hipMemcpyAsync(&total, Z.off.p + nch, sizeof total, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipStreamSynchronize(st));
+  const uint64_t total = scan_lengths(Z.len.p, Z.off.p, nch, Z.tmp, Z.ev[1], st);
   if (total > n + 10 * nch) throw Fail("msw_core_gzip: the chunks' lengths exceed their stored form");
   Z.out.alloc(((total + 3) & ~(uint64_t)3) + 4);
-  gz_pinned_reserve(Z, used + total, used);
+  pinned_reserve(Z.pinned, used + total, used);
   MSW_HIP(hipEventRecord(Z.ev[2], st));
   hipLaunchKernelGGL(k_gz_emit, dim3((unsigned)nch), dim3(kWave), 0, st, d, (uint64_t)n, (uint32_t)nch, Z.tokens.p, Z.tables.p,
                      Z.meta.p, Z.off.p, Z.out.p);
@@ -82,7 +60,7 @@ size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) 
   MSW_HIP(hipEventRecord(Z.ev[3], st));
   uint32_t r = 0;
   MSW_HIP(hipMemcpyAsync(&r, Z.crc.p, sizeof r, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipMemcpyAsync(Z.pinned + used, Z.out.p, total, hipMemcpyDeviceToHost, st));
+  MSW_HIP(hipMemcpyAsync(Z.pinned.p + used, Z.out.p, total, hipMemcpyDeviceToHost, st));
   MSW_HIP(hipStreamSynchronize(st));
   float ms_a = 0.f, ms_b = 0.f;
   MSW_HIP(hipEventElapsedTime(&ms_a, Z.ev[0], Z.ev[1]));
@@ -91,6 +69,17 @@ size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) 
   Z.crc_reg = defl::crc_shift(Z.crc_reg, n, Z.pow8_host) ^ r;
   Z.isize += n;
   return total;
+}
+
+// the same for n bytes of pageable host memory: uploaded (16 bytes of slack behind the next multiple of 16), the copy
+// complete before anything that can fail runs
+size_t gz_compress_host(msw_core *h, const char *bytes, size_t n, size_t used) {
+  GzState &Z = h->gz;
+  if (n == 0) return 0;
+  Z.in.alloc(((n + 15) & ~(size_t)15) + 16);
+  MSW_HIP(hipMemcpyAsync(Z.in.p, bytes, n, hipMemcpyHostToDevice, h->stream));
+  MSW_HIP(hipStreamSynchronize(h->stream));
+  return gz_compress_device(h, Z.in.p, n, used);
 }
 
 // MSWEEP_HOST_GZIP=1: n bytes of host text through zlib; what it gives out appended at `used`
@@ -104,9 +93,9 @@ size_t gz_host_deflate(msw_core *h, const char *p, size_t n, int flush, size_t u
     zs.avail_in = (uInt)in_now;
     left -= in_now;
     do {  // (zlib's idiom: room left over means the input is used up)
-      gz_pinned_reserve(Z, used + got + ((size_t)1 << 18), used + got);
-      const size_t room = std::min<size_t>(Z.pinned_cap - used - got, (size_t)1 << 30);
-      zs.next_out = reinterpret_cast<Bytef *>(Z.pinned + used + got);
+      pinned_reserve(Z.pinned, used + got + ((size_t)1 << 18), used + got);
+      const size_t room = std::min<size_t>(Z.pinned.cap - used - got, (size_t)1 << 30);
+      zs.next_out = reinterpret_cast<Bytef *>(Z.pinned.p + used + got);
       zs.avail_out = (uInt)room;
       if (::deflate(&zs, left ? Z_NO_FLUSH : flush) == Z_STREAM_ERROR) throw Fail("msw_core_gzip: zlib's deflate failed");
       got += room - zs.avail_out;
@@ -151,8 +140,8 @@ void gzip_begin_impl(msw_core *h, int level, const char **out, size_t *len) {
     }
     // RFC 1952: magic, CM 8, no flags, mtime 0, XFL 0, OS 255 (unknown)
     static const unsigned char head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255};
-    gz_pinned_reserve(Z, sizeof head, 0);
-    std::memcpy(Z.pinned, head, sizeof head);
+    pinned_reserve(Z.pinned, sizeof head, 0);
+    std::memcpy(Z.pinned.p, head, sizeof head);
     used = sizeof head;
   }
   Z.open = true;
@@ -168,12 +157,8 @@ void gzip_append_impl(msw_core *h, const char *bytes, size_t n, const char **out
   size_t used = 0;
   if (Z.host) {
     if (n) used = gz_host_deflate(h, bytes, n, Z_NO_FLUSH, 0);
-  } else if (n) {
-    Z.in.alloc(((n + 15) & ~(size_t)15) + 16);
-    // (the caller's bytes are pageable: the copy is complete before anything that can fail runs)
-    MSW_HIP(hipMemcpyAsync(Z.in.p, bytes, n, hipMemcpyHostToDevice, h->stream));
-    MSW_HIP(hipStreamSynchronize(h->stream));
-    used = gz_compress_device(h, Z.in.p, n, 0);
+  } else {
+    used = gz_compress_host(h, bytes, n, 0);
   }
   gz_return(h, used, out, len);
 }
@@ -193,73 +178,17 @@ void gzip_end_impl(msw_core *h, const char **out, size_t *len) {
       tail[2 + i] = (unsigned char)(crc >> (8 * i));
       tail[6 + i] = (unsigned char)(isize >> (8 * i));
     }
-    gz_pinned_reserve(Z, sizeof tail, 0);
-    std::memcpy(Z.pinned, tail, sizeof tail);
+    pinned_reserve(Z.pinned, sizeof tail, 0);
+    std::memcpy(Z.pinned.p, tail, sizeof tail);
     used = sizeof tail;
   }
   gz_close(Z);
   gz_return(h, used, out, len);
 }
 
-// one block of a text output on the device path: its final text compressed where it lies
-size_t gz_text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
-                         size_t used, size_t &n_host, size_t &text_len) {
-  TextState &T = h->text;
-  GzState &Z = h->gz;
-  hipStream_t st = h->stream;
-  const uint32_t cap = text_list_cap();
-  const uint64_t total = text_block_device(h, what, G, w, id0, prefix, n_zero, cap);
-  uint32_t n_list = 0;
-  MSW_HIP(hipMemcpyAsync(&n_list, T.n_list.p, sizeof n_list, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipStreamSynchronize(st));
-  text_add_timing(T, total);
-  if (n_list == 0) {
-    text_len += total;
-    return gz_compress_device(h, T.out.p, total, used);
-  }
-  if (n_list > cap) {
-    // more undecided cells than the list holds: the host formats this block, and its text comes back as host bytes
-    std::vector<double> val;
-    text_block_values(h, what, G, w, val);
-    std::string s;
-    s.reserve(total);
-    text_render_host(what, val, G, w, id0, prefix, n_zero, s);
-    Z.in.alloc(((s.size() + 15) & ~(size_t)15) + 16);
-    MSW_HIP(hipMemcpyAsync(Z.in.p, s.data(), s.size(), hipMemcpyHostToDevice, st));
-    MSW_HIP(hipStreamSynchronize(st));  // (s is pageable and goes at the end of this block, also on a failure)
-    n_host += (size_t)G * w;
-    text_len += s.size();
-    return gz_compress_device(h, Z.in.p, s.size(), used);
-  }
-  // the undecided cells in text order, printed here; k_text_close puts them in and closes the gaps
-  std::vector<TextHostCell> cells(n_list);
-  MSW_HIP(hipMemcpy(cells.data(), T.list.p, n_list * sizeof(TextHostCell), hipMemcpyDeviceToHost));
-  std::sort(cells.begin(), cells.end(), [](const TextHostCell &a, const TextHostCell &b) { return a.off < b.off; });
-  std::vector<GzCell> filled(n_list);
-  uint64_t rp = 0, slack = 0;
-  for (uint32_t i = 0; i < n_list; ++i) {
-    const TextHostCell &c = cells[i];
-    if (c.off < rp || c.off + g6::kMaxLen > total) throw Fail("msw_core_text_block_gzip: an undecided cell lies outside its block");
-    double x;
-    std::memcpy(&x, &c.bits, sizeof x);
-    GzCell &f = filled[i];
-    f.off = c.off;
-    f.slack = (uint32_t)slack;
-    const int n = snprintf(f.s, sizeof f.s, "%g", x);
-    if (n < 1 || n > g6::kMaxLen) throw Fail("msw_core_text_block_gzip: a cell's text does not fit its blanks");
-    f.len = (uint32_t)n;
-    slack += (uint64_t)(g6::kMaxLen - n);
-    rp = c.off + g6::kMaxLen;
-  }
-  Z.cells.upload(filled.data(), n_list, st);
-  MSW_HIP(hipStreamSynchronize(st));  // (`filled` is pageable and goes with this call, also on a failure)
-  Z.closed.alloc((total + 3) & ~(uint64_t)3);
-  hipLaunchKernelGGL(k_text_close, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + 255) / 256, (uint64_t)h->n_cu * 32))),
-                     dim3(256), 0, st, T.out.p, total, Z.cells.p, n_list, Z.closed.p);
-  MSW_HIP(hipGetLastError());
-  n_host += n_list;
-  text_len += total - slack;
-  return gz_compress_device(h, Z.closed.p, total - slack, used);
+// the gzip sink: the finished text of a block compressed where it lies; returns the bytes appended at `used`
+size_t text_sink_gzip(msw_core *h, const TextDone &D, size_t used) {
+  return D.dev ? gz_compress_device(h, D.dev, D.len, used) : gz_compress_host(h, D.host.data(), D.len, used);
 }
 
 void text_block_gzip_impl(msw_core *h, int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero, const char **out,
@@ -275,7 +204,9 @@ void text_block_gzip_impl(msw_core *h, int what, size_t e0, size_t e1, const uin
   } else {
     text_block_check(h, what, e0, e1, prefix, n_zero);
     text_block_each(h, what, e0, e1, prefix, [&](uint32_t G, size_t w, size_t j0, const uint64_t *pre) {
-      used += gz_text_block_run(h, what, G, w, j0, pre, n_zero, used, n_host, text_len);
+      const TextDone D = text_block_finish(h, what, G, w, j0, pre, n_zero, n_host);
+      text_len += D.len;
+      used += text_sink_gzip(h, D, used);
     });
   }
   gz_return(h, used, out, len);

@@ -1,8 +1,10 @@
 // host_text.inc -- msw_core_text_block / msw_core_format_g6 (included by msweep_core.hip): the text of the matrix
-// outputs formatted on the device (text_kernels.hpp).  Per block of ECs: materialise the G x w values where they lie
-// (host_likelihood.inc), the length of every line, an exclusive scan, the write pass, one copy of the bytes to the
-// handle's pinned buffer.  Device memory: the block, its text and O(w) offsets; nothing is sized G x E.  The few cells
-// the device leaves undecided come back as (byte offset, bits): the host prints them with snprintf and closes the gaps.
+// outputs formatted on the device (text_kernels.hpp).  One pipeline per block of ECs, shared with the gzip stream
+// (host_gzip.inc): materialise the G x w values where they lie (host_likelihood.inc), the length of every line, an
+// exclusive scan, the write pass -- the block's FINISHED text (text_block_finish) -- and a sink: here one copy of the
+// bytes to the handle's pinned buffer, there the compressor.  The few cells the device leaves undecided come back as
+// (byte offset, bits): the host prints them (text_cells.hpp), k_text_close puts them in and closes the gaps; more of
+// them than the list holds: the host formats the block.  Device memory: the block, its text and O(w) offsets.
 namespace {
 
 constexpr size_t kTextMaxBytes = (size_t)1 << 30;  // worst-case text of one call
@@ -15,18 +17,34 @@ uint32_t text_list_cap() {
   return kTextListCap;
 }
 
-void text_pinned_reserve(TextState &T, size_t need, size_t used) {
-  if (need <= T.pinned_cap) return;
-  const size_t cap = std::max(need, T.pinned_cap + T.pinned_cap / 2);
+// room for `need` bytes in a pinned buffer, its first `keep` bytes kept
+void pinned_reserve(PinnedBuf &B, size_t need, size_t keep) {
+  if (need <= B.cap) return;
+  const size_t cap = std::max(need, B.cap + B.cap / 2);
   char *p = nullptr;
   if (hipHostMalloc((void **)&p, cap, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();
-    throw Fail("msw_core_text_block: cannot allocate " + std::to_string(cap) + " bytes of pinned host memory for the text");
+    throw Fail(std::string(B.who) + ": cannot allocate " + std::to_string(cap) + " bytes of pinned host memory for " + B.what);
   }
-  if (used) std::memcpy(p, T.pinned, used);
-  if (T.pinned) (void)hipHostFree(T.pinned);
-  T.pinned = p;
-  T.pinned_cap = cap;
+  if (keep) std::memcpy(p, B.p, keep);
+  if (B.p) (void)hipHostFree(B.p);
+  B.p = p;
+  B.cap = cap;
+}
+
+// off[i] = len[0] + ... + len[i - 1] for i in [0, n], len[n] a spare zero; `scanned` is recorded behind the scan, and
+// off[n], the total, comes back with the stream synchronised
+uint64_t scan_lengths(const uint32_t *len, uint64_t *off, size_t n, DevBuf<uint8_t> &tmp, hipEvent_t scanned, hipStream_t st) {
+  auto len64 = rocprim::make_transform_iterator(len, U32ToU64{});
+  size_t tmp_bytes = 0;
+  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, off, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), st));
+  tmp.alloc(tmp_bytes);
+  MSW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, len64, off, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(hipEventRecord(scanned, st));
+  uint64_t total = 0;
+  MSW_HIP(hipMemcpyAsync(&total, off + n, sizeof total, hipMemcpyDeviceToHost, st));
+  MSW_HIP(hipStreamSynchronize(st));
+  return total;
 }
 
 size_t text_dec(char *p, uint64_t v) { return (size_t)snprintf(p, 24, "%llu", (unsigned long long)v); }
@@ -98,95 +116,91 @@ uint64_t text_block_device(msw_core *h, int what, uint32_t G, size_t w, uint64_t
     if (!e) MSW_HIP(hipEventCreate(&e));
   MSW_HIP(hipEventRecord(T.ev[0], st));
   text_launch_what(h, what, J, T, cap, false);
-  auto len64 = rocprim::make_transform_iterator(T.len.p, U32ToU64{});
-  size_t tmp_bytes = 0;
-  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, T.off.p, (uint64_t)0, w + 1, rocprim::plus<uint64_t>(), st));
-  T.tmp.alloc(tmp_bytes);
-  MSW_HIP(rocprim::exclusive_scan(T.tmp.p, tmp_bytes, len64, T.off.p, (uint64_t)0, w + 1, rocprim::plus<uint64_t>(), st));
-  MSW_HIP(hipEventRecord(T.ev[1], st));
-  uint64_t total = 0;
-  MSW_HIP(hipMemcpyAsync(&total, T.off.p + w, sizeof total, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipStreamSynchronize(st));
+  const uint64_t total = scan_lengths(T.len.p, T.off.p, w, T.tmp, T.ev[1], st);
   T.out.alloc((total + 3) & ~(uint64_t)3);
   MSW_HIP(hipEventRecord(T.ev[2], st));
   text_launch_what(h, what, J, T, cap, true);
   MSW_HIP(hipEventRecord(T.ev[3], st));
   return total;
 }
-// (after the stream has been synchronised behind text_block_device)
-void text_add_timing(TextState &T, uint64_t total) {
+
+// the finished text of a block, every cell printed: where it lies on the device (16-byte aligned, readable up to the
+// next multiple of 4; T.out or T.closed, until the next block) or, from the whole-block host render, as host bytes
+struct TextDone {
+  const uint8_t *dev = nullptr;  // null: `host` holds the text
+  std::string host;
+  size_t len = 0;
+};
+
+// The block whose values lie in T.val, finished; the cells the host printed are added to n_host.
+TextDone text_block_finish(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
+                           size_t &n_host) {
+  TextState &T = h->text;
+  hipStream_t st = h->stream;
+  const uint32_t cap = text_list_cap();
+  const uint64_t total = text_block_device(h, what, G, w, id0, prefix, n_zero, cap);
+  uint32_t n_list = 0;
+  MSW_HIP(hipMemcpyAsync(&n_list, T.n_list.p, sizeof n_list, hipMemcpyDeviceToHost, st));
+  MSW_HIP(hipStreamSynchronize(st));
   float ms_len = 0.f, ms_write = 0.f;
   MSW_HIP(hipEventElapsedTime(&ms_len, T.ev[0], T.ev[1]));
   MSW_HIP(hipEventElapsedTime(&ms_write, T.ev[2], T.ev[3]));
   T.kernel_ms += (double)ms_len + (double)ms_write;
   T.bytes += total;
-}
-// PROBS on a block the host formats itself: the values the device formats, on the host
-void text_block_values(msw_core *h, int what, uint32_t G, size_t w, std::vector<double> &val) {
-  TextState &T = h->text;
-  const size_t n = (size_t)G * w;
-  if (what == kTextProbs) {
-    hipLaunchKernelGGL(k_text_exp, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, h->stream, T.val.p, n);
-    MSW_HIP(hipGetLastError());
-  }
-  val.resize(n);
-  MSW_HIP(hipMemcpyAsync(val.data(), T.val.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  MSW_HIP(hipStreamSynchronize(h->stream));
-}
-
-// The same text appended to the pinned buffer at `used`, the undecided cells filled in; returns the bytes appended.
-size_t text_block_run(msw_core *h, int what, uint32_t G, size_t w, uint64_t id0, const uint64_t *prefix, size_t n_zero,
-                      size_t used, size_t &n_host) {
-  TextState &T = h->text;
-  hipStream_t st = h->stream;
-  const uint32_t cap = text_list_cap();
-  const uint64_t total = text_block_device(h, what, G, w, id0, prefix, n_zero, cap);
-  text_pinned_reserve(T, used + total, used);
-  uint32_t n_list = 0;
-  MSW_HIP(hipMemcpyAsync(&n_list, T.n_list.p, sizeof n_list, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipMemcpyAsync(T.pinned + used, T.out.p, total, hipMemcpyDeviceToHost, st));
-  MSW_HIP(hipStreamSynchronize(st));
-  text_add_timing(T, total);
-  if (n_list == 0) return total;
-  char *text = T.pinned + used;
+  TextDone D{T.out.p, std::string(), total};
+  if (n_list == 0) return D;
   if (n_list > cap) {
     // more undecided cells than the list holds: the host formats this block from the values the device formatted
-    std::vector<double> val;
-    text_block_values(h, what, G, w, val);
-    std::string s;
-    s.reserve(total);
-    text_render_host(what, val, G, w, id0, prefix, n_zero, s);
-    if (s.size() > total) throw Fail("msw_core_text_block: the host's text of a block is longer than the device's");
-    std::memcpy(text, s.data(), s.size());
-    n_host += (size_t)G * w;
-    return s.size();
+    // (PROBS: the device's exp of them)
+    const size_t n = (size_t)G * w;
+    if (what == kTextProbs) {
+      hipLaunchKernelGGL(k_text_exp, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, st, T.val.p, n);
+      MSW_HIP(hipGetLastError());
+    }
+    std::vector<double> val(n);
+    MSW_HIP(hipMemcpyAsync(val.data(), T.val.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    MSW_HIP(hipStreamSynchronize(st));
+    D.host.reserve(total);
+    text_render_host(what, val, G, w, id0, prefix, n_zero, D.host);
+    if (D.host.size() > total) throw Fail("msw_core_text_block: the host's text of a block is longer than the device's");
+    D.dev = nullptr;
+    D.len = D.host.size();
+    n_host += n;
+    return D;
   }
-  // the undecided cells in text order: print each into its 13 blanks and move what follows up against it
+  // the undecided cells in text order, printed here; k_text_close puts them in and closes the gaps
   std::vector<TextHostCell> cells(n_list);
   MSW_HIP(hipMemcpy(cells.data(), T.list.p, n_list * sizeof(TextHostCell), hipMemcpyDeviceToHost));
   std::sort(cells.begin(), cells.end(), [](const TextHostCell &a, const TextHostCell &b) { return a.off < b.off; });
-  size_t rp = 0, wp = 0;
-  char b[32];
-  for (const TextHostCell &c : cells) {
-    if (c.off < rp || c.off + g6::kMaxLen > total) throw Fail("msw_core_text_block: an undecided cell lies outside its block");
-    std::memmove(text + wp, text + rp, c.off - rp);
-    wp += c.off - rp;
-    double x;
-    std::memcpy(&x, &c.bits, sizeof x);
-    const int n = snprintf(b, sizeof b, "%g", x);
-    std::memcpy(text + wp, b, (size_t)n);
-    wp += (size_t)n;
-    rp = c.off + g6::kMaxLen;
-  }
-  std::memmove(text + wp, text + rp, total - rp);
-  wp += total - rp;
+  std::vector<TextFilledCell> filled;
+  D.len = text_fill_cells(cells, total, filled);
+  T.cells.upload(filled.data(), n_list, st);
+  MSW_HIP(hipStreamSynchronize(st));  // (`filled` is pageable and goes with this call, also on a failure)
+  T.closed.alloc((total + 3) & ~(uint64_t)3);
+  hipLaunchKernelGGL(k_text_close, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((total + 255) / 256, (uint64_t)h->n_cu * 32))),
+                     dim3(256), 0, st, T.out.p, total, T.cells.p, n_list, T.closed.p);
+  MSW_HIP(hipGetLastError());
+  D.dev = T.closed.p;
   n_host += n_list;
-  return wp;
+  return D;
+}
+
+// the plain sink: the finished text appended to the pinned buffer at `used`; returns the bytes appended
+size_t text_sink_plain(msw_core *h, const TextDone &D, size_t used) {
+  TextState &T = h->text;
+  pinned_reserve(T.pinned, used + D.len, used);
+  if (D.dev) {
+    MSW_HIP(hipMemcpyAsync(T.pinned.p + used, D.dev, D.len, hipMemcpyDeviceToHost, h->stream));
+    MSW_HIP(hipStreamSynchronize(h->stream));
+  } else {
+    std::memcpy(T.pinned.p + used, D.host.data(), D.len);
+  }
+  return D.len;
 }
 
 void text_return(msw_core *h, size_t used, size_t n_host, const char **text_out, size_t *len_out, size_t *n_host_out) {
-  text_pinned_reserve(h->text, 1, 0);  // an empty text still points somewhere
-  *text_out = h->text.pinned;
+  pinned_reserve(h->text.pinned, 1, 0);  // an empty text still points somewhere
+  *text_out = h->text.pinned.p;
   *len_out = used;
   if (n_host_out) *n_host_out = n_host;
 }
@@ -240,7 +254,7 @@ void text_block_impl(msw_core *h, int what, size_t e0, size_t e1, const uint64_t
   text_block_check(h, what, e0, e1, prefix, n_zero);
   size_t used = 0, n_host = 0;
   text_block_each(h, what, e0, e1, prefix, [&](uint32_t G, size_t w, size_t j0, const uint64_t *pre) {
-    used += text_block_run(h, what, G, w, j0, pre, n_zero, used, n_host);
+    used += text_sink_plain(h, text_block_finish(h, what, G, w, j0, pre, n_zero, n_host), used);
   });
   text_return(h, used, n_host, text_out, len_out, n_host_out);
 }
@@ -256,7 +270,7 @@ void format_g6_impl(msw_core *h, const double *x, size_t n, const char **text_ou
   for (size_t i0 = 0; i0 < n; i0 += blk) {
     const size_t w = std::min(blk, n - i0);
     h->text.val.upload(x + i0, w, h->stream);
-    used += text_block_run(h, kTextPlain, 1, w, 0, nullptr, 0, used, n_host);
+    used += text_sink_plain(h, text_block_finish(h, kTextPlain, 1, w, 0, nullptr, 0, n_host), used);
   }
   text_return(h, used, n_host, text_out, len_out, n_host_out);
 }

@@ -181,24 +181,35 @@ struct Worker {  // a bootstrap worker: replicates on a stream of their own, bes
   ~Worker() { (void)hipStreamDestroy(s.stream); }
 };
 
+// pinned host bytes handed to the caller, valid until the next call of their family; grown by pinned_reserve
+// (host_text.inc), which words its failure "<who>: cannot allocate ... for <what>"
+struct PinnedBuf {
+  const char *who, *what;
+  char *p = nullptr;
+  size_t cap = 0;
+  PinnedBuf(const char *who_, const char *what_) : who(who_), what(what_) {}
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
+
 // ---- what msw_core_text_block / msw_core_format_g6 keep between calls (host_text.inc) ----------------------------
 struct TextState {
-  char *pinned = nullptr;  // the text handed to the caller, valid until the next call
-  size_t pinned_cap = 0;
+  PinnedBuf pinned{"msw_core_text_block", "the text"};
   DevBuf<double> val;      // the G x w block of values
-  DevBuf<uint8_t> out, tmp;
+  DevBuf<uint8_t> out, tmp, closed;  // the text as written; scan scratch; the text with its undecided cells closed
   DevBuf<uint32_t> len, n_list;
   DevBuf<uint64_t> off, prefix;
   DevBuf<TextHostCell> list;
+  DevBuf<TextFilledCell> cells;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the length pass + scan, around the write pass
   double kernel_ms = 0.0;  // of the last call (msw_core_last_text_timing)
   uint64_t bytes = 0;
   void release_device() {
-    val.release(); out.release(); tmp.release(); len.release(); n_list.release(); off.release(); prefix.release();
-    list.release();
+    val.release(); out.release(); tmp.release(); closed.release(); len.release(); n_list.release(); off.release();
+    prefix.release(); list.release(); cells.release();
   }
   ~TextState() {
-    if (pinned) (void)hipHostFree(pinned);
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -211,24 +222,21 @@ struct GzState {
   uint32_t crc_reg = 0;  // the CRC register over the text so far (deflate_format.hpp: R(~0, text))
   uint64_t isize = 0;    // ... and its length
   std::unique_ptr<z_stream> zs;
-  char *pinned = nullptr;  // the compressed bytes handed to the caller, valid until the next call
-  size_t pinned_cap = 0;
-  DevBuf<uint8_t> in, closed, out, tmp;  // uploaded host bytes; a text block with its undecided cells closed; the chunks
+  PinnedBuf pinned{"msw_core_gzip", "the compressed bytes"};
+  DevBuf<uint8_t> in, out, tmp;  // uploaded host bytes; the chunks; scan scratch
   DevBuf<uint32_t> tokens, tables, len, crc, pow8;
   DevBuf<GzChunk> meta;
   DevBuf<uint64_t> off;
-  DevBuf<GzCell> cells;
   uint32_t pow8_host[40] = {};
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around parse + CRC + scan, around the emit pass
   double kernel_ms = 0.0;  // of the stream (msw_core_last_gzip_timing)
   uint64_t bytes_out = 0;
   void release_device() {
-    in.release(); closed.release(); out.release(); tmp.release(); tokens.release(); tables.release(); len.release();
-    meta.release(); off.release(); cells.release();
+    in.release(); out.release(); tmp.release(); tokens.release(); tables.release(); len.release(); meta.release();
+    off.release();
   }
   ~GzState() {
     if (zs) (void)deflateEnd(zs.get());
-    if (pinned) (void)hipHostFree(pinned);
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
   }

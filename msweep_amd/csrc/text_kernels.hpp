@@ -19,10 +19,13 @@
 // registers, digits in nibbles, never in an indexed array.
 //
 // A value the formatter cannot decide (g6::kUndecided: too close to a half where the power of ten is inexact) gets 13
-// blanks, and its (byte offset, bits) goes to a list the host fills in and closes up (host_text.inc).
+// blanks, and its (byte offset, bits) goes to a list: the host prints those cells (text_cells.hpp) and
+//   k_text_close  puts them in: every stretch between them moves down by the slack accumulated in front of it, and the
+//                 finished text lies on the device for either sink, the copy to the host or the compressor (host_gzip.inc).
 #pragma once
 #include "common.hpp"
 #include "g6_format.hpp"
+#include "text_cells.hpp"
 
 namespace msw {
 
@@ -37,10 +40,6 @@ constexpr int kTextWaves = kTextThreads / kWave;
 constexpr int kTextStageBytes = 1024;
 static_assert(3 + 21 + kTextGroups * 25 <= kTextStageBytes, "a stretch must fit the staging area");
 constexpr int kTextSuffixPiece = 512;  // bytes of a line's suffix staged at a time
-
-struct TextHostCell {  // a cell left to the host: where its 13 blanks start, and the bits of the value
-  uint64_t off, bits;
-};
 
 struct TextJob {
   const double *val;       // G x w, group-major
@@ -242,6 +241,30 @@ __global__ __launch_bounds__(kTextThreads) void k_text_write(TextJob J, const ui
         text_wave_sync();
       }
     }
+  }
+}
+
+// dst <- src[0 .. total) with every listed cell's 13 blanks replaced by its text; cells sorted by offset
+__global__ __launch_bounds__(256) void k_text_close(const uint8_t *__restrict__ src, uint64_t total, const TextFilledCell *__restrict__ cells,
+                                                    uint32_t n_cells, uint8_t *__restrict__ dst) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t lo = 0, hi = n_cells;  // lo <- the cells that start at or before byte i
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (cells[mid].off <= i) lo = mid + 1;
+      else hi = mid;
+    }
+    uint64_t slack = 0;
+    if (lo) {
+      const TextFilledCell *c = &cells[lo - 1];
+      const uint64_t j = i - c->off;
+      if (j < (uint64_t)g6::kMaxLen) {
+        if (j < c->len) dst[c->off - c->slack + j] = (uint8_t)c->s[j];
+        continue;
+      }
+      slack = (uint64_t)c->slack + ((uint32_t)g6::kMaxLen - c->len);
+    }
+    dst[i - slack] = src[i];
   }
 }
 

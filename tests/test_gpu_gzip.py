@@ -4,6 +4,9 @@ input, for host bytes of every size around the 32 KiB chunk and of every kind of
 on the layouts of tests/test_gpu_text_format.py; the conditions on its size (stored chunks for random bytes, matches and
 dynamic codes on probs-shaped text), determinism, level 0, the zlib path behind MSWEEP_HOST_GZIP=1, and the refusals."""
 import gzip
+import hashlib
+import json
+import os
 import zlib
 
 import numpy as np
@@ -224,3 +227,42 @@ def test_undecided_cells_are_closed_on_the_device(monkeypatch, cap):
                 assert cells >= n_ties          # whole blocks (those with more undecided cells than the list holds)
         out, plain, _ = _gz_blocks(core, TEXT_BITSEQ, 290, step=41)
         one_member(out, plain)
+
+
+# ---- the streams pinned ------------------------------------------------------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gzip_streams.json")
+
+
+def pinned_streams(setenv, delenv):
+    """(name, stream) of the calls tests/golden/gzip_streams.json pins: a fixed gzip_append input, and the 5 x 300 tie matrix
+    of test_undecided_cells_are_closed_on_the_device as LOGL in ranges of 37 classes and of E, with the whole list and with
+    a list of two entries.  Only the Core API: the same function runs on any build of the library."""
+    setenv("MSWEEP_DENSE_COMPRESS", "0")
+    delenv("MSWEEP_TEXT_HOST_CAP", raising=False)
+    delenv("MSWEEP_HOST_GZIP", raising=False)
+    rng = np.random.default_rng(3)
+    G, E = 5, 300
+    L = -50.0 * rng.random((G, E))
+    L[rng.integers(0, G, 60), rng.integers(0, E, 60)] = [-float((2 * int(n) + 1) * 5) for n in rng.integers(100000, 1000000, 60)]
+    prefix = np.arange(E, dtype=np.uint64)
+    with Core(0) as core:
+        yield "append_probs_text", stream(core, [probs_text(3 * C + 7, seed=5)])
+        from_dense(core, L, np.zeros(E))
+        for cap in (None, "2"):
+            if cap:
+                setenv("MSWEEP_TEXT_HOST_CAP", cap)
+            for step in (37, E):
+                out, plain, _ = _gz_blocks(core, TEXT_LOGL, E, step=step, line_prefix=prefix)
+                one_member(out, plain)
+                yield f"ties_logl_step{step}_cap{cap}", out
+
+
+def test_compressed_streams_are_the_recorded_ones(monkeypatch):
+    """the compressed bytes are a function of the text, the chunk size and the call boundaries: length and SHA-256 of the
+    streams above against tests/golden/gzip_streams.json, recorded once from the library as it was before the text and
+    gzip outputs shared their block pipeline"""
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = {name: {"len": len(out), "sha256": hashlib.sha256(out).hexdigest()} for name, out in pinned_streams(monkeypatch.setenv, monkeypatch.delenv)}
+    assert len(got) == 5
+    assert got == want

@@ -283,3 +283,57 @@ def test_text_block_undecided_cells_in_a_matrix(monkeypatch):
             assert text == render_logl(L, 0, E, prefix)
             assert n_host == (G * E if cap else n_ties)
             assert core.text_block(TEXT_BITSEQ, 3, 290) == render_bitseq(L, 3, 290)
+
+
+# ---- 4. the smallest blocks with undecided cells: their gaps are closed on the device -----------------------------------
+T_LONG, T_SHORT, X = 1234565.0, 1000005.0, 0.25       # two ties of the kind above (11 bytes and, half to even, "1e+06"); X is ordinary
+
+
+def _tie_arrays():
+    for t in (T_LONG, T_SHORT):
+        yield [t]
+        yield [t, t, t]
+        yield [X, t]
+        yield [t, X]
+        x = [X, -X, 1e-5] * 21 + [X, X]                 # 65 values: ties at 0, 63 and 64, the edge of k_text_write's 64-line tile
+        x[0], x[63], x[64] = t, T_LONG, t
+        yield x
+
+
+def _caps(monkeypatch, n_ties, n_cells):
+    """(n_host expected) under the whole list, a list of exactly n_ties entries (the list path still) and one entry fewer
+    (the host formats the block)"""
+    monkeypatch.delenv("MSWEEP_TEXT_HOST_CAP", raising=False)
+    yield n_ties
+    monkeypatch.setenv("MSWEEP_TEXT_HOST_CAP", str(n_ties))
+    yield n_ties
+    monkeypatch.setenv("MSWEEP_TEXT_HOST_CAP", str(n_ties - 1))
+    yield n_cells
+
+
+def test_format_smallest_blocks_with_ties(gpu_core, monkeypatch):
+    assert g6(T_LONG) == b"1.23456e+06" and g6(T_SHORT) == b"1e+06"
+    for x in _tie_arrays():
+        n_ties = sum(v in (T_LONG, T_SHORT) for v in x)
+        for want_host in _caps(monkeypatch, n_ties, len(x)):
+            text, n_host = gpu_core.format_g6(np.array(x), with_host_cells=True)
+            assert text == lines_of(x), x
+            assert n_host == want_host, x
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_text_block_smallest_all_tie_matrices(monkeypatch, n):
+    """dense n x n, every cell a tie: LOGL, and BITSEQ where a suffix follows the last cell"""
+    monkeypatch.setenv("MSWEEP_DENSE_COMPRESS", "0")
+    L = -np.array([[T_LONG, T_SHORT], [T_SHORT, T_LONG]])[:n, :n]
+    prefix = np.arange(n, dtype=np.uint64) + np.uint64(7)
+    with Core(0) as core:
+        from_dense(core, L, np.zeros(n))
+        np.testing.assert_array_equal(core.get_dense_logl(), L)
+        for want_host in _caps(monkeypatch, n * n, n * n):
+            text, n_host = core.text_block(TEXT_LOGL, 0, n, line_prefix=prefix, with_host_cells=True)
+            assert text == render_logl(L, 0, n, prefix)
+            assert n_host == want_host
+            text, n_host = core.text_block(TEXT_BITSEQ, 0, n, with_host_cells=True)
+            assert text == render_bitseq(L, 0, n)
+            assert n_host == want_host
