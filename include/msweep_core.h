@@ -378,7 +378,9 @@ const char *msw_comm_last_error(void);
  * (Alignment::reads_assigned_to_ec, :229: the read ids of every EC, ascending).  n_reads is the line
  * count of the last strand (Alignment::n_reads, :219).  Any output pointer may be NULL.
  * gzip-compressed files (Themisto --gzip-output; the reference opens its inputs through bxzstr, which detects
- * the compression by its magic bytes) are inflated with zlib; bzip2 / xz files are refused by name.
+ * the compression by its magic bytes) are inflated with zlib by msw_alignment_read, and on the device by
+ * msw_alignment_read_device (below: msw_inflate_info), with zlib behind it wherever the device's result cannot be
+ * vouched for; bzip2 / xz files are refused by name.
  * The compact alignment-writer format is not supported (BitMagic): convert to plaintext. */
 typedef struct msw_alignment *msw_alignment_t;
 #define MSW_MERGE_INTERSECTION 0
@@ -403,6 +405,37 @@ void msw_alignment_destroy(msw_alignment_t a);
  * (msw_alignment_last_error / msw_last_error). */
 int msw_alignment_read_device(msw_handle h, const char *const *paths, size_t n_paths, size_t n_targets, int merge_mode,
                               msw_alignment_t *out);
+/* gzip input of msw_alignment_read_device is inflated ON THE DEVICE (msweep_amd/csrc/host_inflate.inc): the compressed
+ * bytes cross the link, a probe finds block starts inside the stream, the chunks between them are decoded side by side
+ * against an unknown 32 KiB window, the windows are resolved in order and a second pass writes the text where the token
+ * kernels read it.  The member's trailer is the guarantee: the device's text is used only when its CRC-32 and length are
+ * the ones the file promises; otherwise -- and for several members, trailing bytes, a header the parser does not take,
+ * a payload that does not fit, a stream with too few block starts for the device to pay -- zlib inflates the same file on the host, result and messages as before.
+ * MSWEEP_HOST_INFLATE=1 in the environment (developer switch, read at the call) forces the host path. */
+typedef struct msw_inflate_info {
+  uint64_t payload_bytes, text_bytes;
+  uint32_t chunk_bytes, n_chunks, n_starts;   /* chunks that begin at a block start the probe found (chunk 0 included) */
+  int32_t on_device;                          /* 1: the bytes returned were inflated by the kernels and passed the trailer check */
+  int32_t fallback_reason;                    /* 0 none; 1 forced, 2 header, 3 probe mismatch, 4 chunk status, 5 crc or length,
+                                               * 6 trailing bytes, 7 memory, 8 long span (a stretch between two block
+                                               * starts too long for one wavefront to pay: fixed-Huffman or stored
+                                               * streams, one very long block) */
+  double kernel_ms;                           /* events on the handle's stream: probe through CRC */
+  double upload_ms;                           /* host clock: the compressed bytes to the device (files only) */
+  double probe_ms, window_ms, chain_ms, write_ms, crc_ms; /* the parts of kernel_ms: probe, pass (a) with the scan, window
+                                               * chain, pass (b), CRC -- each a pair of events directly around its
+                                               * launches (a second strand shares the stream with the first one's token
+                                               * kernels, which can fall inside a pair) */
+} msw_inflate_info;
+/* Test and diagnostic entry (the role msw_core_format_g6 has for the formatter): the text of the gzip bytes gz[0 .. n),
+ * inflated by the kernels (chunk_bytes of payload per chunk; 0: the default, or MSWEEP_INFLATE_CHUNK) or, where their
+ * result cannot be vouched for, by zlib (every member, as gzread reads a file).  *text_out is valid until the next
+ * call; bytes that zlib rejects too fail the call with zlib's message. */
+int msw_core_inflate_gzip(msw_handle h, const uint8_t *gz, size_t n, size_t chunk_bytes /* 0 = default */,
+                          const uint8_t **text_out, size_t *len_out, msw_inflate_info *info);
+/* One entry per file of the last msw_alignment_read_device on h, in the order of its paths (a plain file: all zero but
+ * text_bytes): which path served each strand.  At most max_files entries are written; *n_files = how many there are. */
+int msw_alignment_last_inflate(msw_handle h, msw_inflate_info *info, size_t max_files, size_t *n_files);
 /* 1: the handle's arrays are device-resident (msw_alignment_read_device served the text with its kernels); 0: host
  * arrays (msw_alignment_read, or the host parser behind the device entry). */
 int msw_alignment_on_device(msw_alignment_t a);

@@ -314,6 +314,12 @@ def main(argv=None):
             # the reader on the device (msw_alignment_read_device): text -> equivalence classes in HBM, consumed there
             # by the likelihood build; the reference's messages for text it does not take
             aln = core.read_alignment(files, len(grouping.group_indicators), a.themisto_mode)
+            if a.verbose:
+                # gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
+                for path, info in zip(files, core.last_inflate()):
+                    if info["payload_bytes"] or info["fallback_reason"]:
+                        how = "the device" if info["on_device"] else f"the host ({info['reason']})"
+                        sys.stderr.write(f"note: {path}: gzip input inflated on {how}\n")
     except (RuntimeError, OSError, MswError) as ex:
         sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
         return 1

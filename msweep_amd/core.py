@@ -37,11 +37,28 @@ EXPORTS = [
     "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
+    "msw_core_inflate_gzip", "msw_alignment_last_inflate",
 ]
+
+# msw_inflate_info.fallback_reason
+INFLATE_REASONS = ("none", "forced", "header", "probe mismatch", "chunk status", "crc", "trailing bytes", "memory", "long span")
 
 
 class MswError(RuntimeError):
     """Non-zero return from the C ABI (mirrors the std::runtime_error the C++ shim throws)."""
+
+
+class InflateInfo(C.Structure):
+    """msw_inflate_info: how a gzip input was inflated (Core.inflate_gzip, Core.last_inflate)"""
+    _fields_ = [("payload_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("chunk_bytes", C.c_uint32), ("n_chunks", C.c_uint32),
+                ("n_starts", C.c_uint32), ("on_device", C.c_int32), ("fallback_reason", C.c_int32), ("kernel_ms", C.c_double),
+                ("upload_ms", C.c_double), ("probe_ms", C.c_double), ("window_ms", C.c_double), ("chain_ms", C.c_double),
+                ("write_ms", C.c_double), ("crc_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["reason"] = INFLATE_REASONS[self.fallback_reason] if 0 <= self.fallback_reason < len(INFLATE_REASONS) else "?"
+        return d
 
 
 class Timing(C.Structure):
@@ -136,6 +153,8 @@ def load_library():
     L.msw_core_gzip_append.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz)]
     L.msw_core_gzip_end.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.msw_core_last_gzip_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.msw_core_inflate_gzip.argtypes = [vp, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(InflateInfo)]
+    L.msw_alignment_last_inflate.argtypes = [vp, C.POINTER(InflateInfo), sz, C.POINTER(sz)]
     L.msw_core_trace.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.msw_core_set_trace_theta.argtypes = [vp, sz]
     L.msw_core_bootstrap.argtypes = [vp, vp, C.c_int32, sz, sz, sz, vp, dp, sz, C.c_int, C.c_int, vp, vp]
@@ -536,6 +555,25 @@ class Core:
         ms, ni, no = C.c_double(), C.c_uint64(), C.c_uint64()
         self._check(self._L.msw_core_last_gzip_timing(self._h, C.byref(ms), C.byref(ni), C.byref(no)))
         return ms.value, ni.value, no.value
+
+    # ---- gzip input inflated on the device (msw_core_inflate_gzip: the decoder's test and diagnostic entry)
+    def inflate_gzip(self, data, chunk_bytes=0):
+        """(text, info) of gzip bytes: inflated by the kernels -- chunk_bytes of payload per chunk, 0 the default -- or, where
+        their result cannot be vouched for, by zlib; info is msw_inflate_info as a dict (on_device, reason, n_starts ...)."""
+        data = bytes(data)
+        p, n, info = C.c_void_p(), C.c_size_t(), InflateInfo()
+        self._check(self._L.msw_core_inflate_gzip(self._h, data if data else None, len(data), int(chunk_bytes), C.byref(p), C.byref(n),
+                                                  C.byref(info)))
+        return (C.string_at(p.value, n.value) if n.value else b""), info.as_dict()
+
+    def last_inflate(self):
+        """One dict per file of the last read_alignment on this handle (msw_alignment_last_inflate): which path inflated
+        each strand -- on_device, reason, chunks, starts, stage times; a plain file has only text_bytes."""
+        n = C.c_size_t()
+        self._check(self._L.msw_alignment_last_inflate(self._h, None, 0, C.byref(n)))
+        infos = (InflateInfo * max(1, n.value))()
+        self._check(self._L.msw_alignment_last_inflate(self._h, infos, n.value, C.byref(n)))
+        return [infos[i].as_dict() for i in range(n.value)]
 
     def bin_reads(self, ec_rptr, ec_reads, targets, thresholds, want_reads=True):
         """mGEMS read binning of the last solve on the device (msw_core_bin_reads): the reads of EC j go to bin k when

@@ -587,6 +587,19 @@ int main(int argc, char **argv) {
       if (msw_alignment_read_device(h, paths.data(), paths.size(), grouping.indicators.size(),
                                     a.mode == "union" ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION, &aln))
         throw std::runtime_error(msw_alignment_last_error());
+      if (a.verbose) {
+        // gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
+        static const char *const why[] = {"none", "forced", "header", "probe mismatch", "chunk status", "crc", "trailing bytes", "memory", "long span"};
+        std::vector<msw_inflate_info> info(paths.size());
+        size_t n_info = 0;
+        if (msw_alignment_last_inflate(h, info.data(), info.size(), &n_info) == 0)
+          for (size_t i = 0; i < std::min(n_info, info.size()); ++i) {
+            if (!info[i].payload_bytes && !info[i].fallback_reason) continue;
+            std::cerr << "note: " << paths[i] << ": gzip input inflated on ";
+            if (info[i].on_device) std::cerr << "the device\n";
+            else std::cerr << "the host (" << why[info[i].fallback_reason >= 0 && info[i].fallback_reason < 9 ? info[i].fallback_reason : 0] << ")\n";
+          }
+      }
       msw_alignment_shape(aln, &n_ecs, &n_reads, &n_hits, &n_aligned);
       ec_counts.resize(n_ecs);
       msw_alignment_export(aln, nullptr, nullptr, ec_counts.data(), nullptr, nullptr);

@@ -50,6 +50,7 @@ struct ReaderCtx {
   TextStager *stage;
   ReaderPool *pool;
   int device = 0;
+  InflateState *inf = nullptr;      // the handle's gzip-input state (host_inflate.inc)
   RBuf<unsigned char> tmp{*this};   // rocPRIM's temporary storage
   RBuf<ReaderCtr> ctr{*this};
   bool timing = false;
@@ -104,7 +105,8 @@ void scan_u32_u64(const uint32_t *in, uint64_t *out, size_t n, ReaderCtx &cx) {
 
 // The text of one file in device memory, padded with line feeds to whole tiles (+ one: the parse kernel reads 16 bytes
 // behind every segment).  Plain files are read with pread() on the reader's threads straight into pinned memory, one
-// chunk on its way to the device while the next is read; gzip files are inflated by the host reader's slurp_text first.
+// chunk on its way to the device while the next is read; gzip files travel compressed and are inflated by the kernels
+// of inflate_kernels.hpp (host_inflate.inc), or, where that result cannot be vouched for, by the host reader's slurp_text.
 // The copies run on the stager's own stream (`done` marks the last one): read_alignment_device sends the NEXT strand's
 // text while this strand's kernels run.
 struct DevText {
@@ -119,6 +121,47 @@ struct DevText {
     if (done) (void)hipEventDestroy(done);
   }
 };
+// n bytes -- of the open file fd, or of host memory `mem` when that is not null -- to dev through the stager, on its copy
+// stream; last: the last of them
+void stager_ready(ReaderCtx &cx) {
+  // (reader threads: beyond ~8 the page-cache copies of these hosts stop scaling and only contend; MSWEEP_READER_THREADS
+  // decides when set)
+  const size_t T0 = getenv("MSWEEP_READER_THREADS") ? reader_threads() : std::min<size_t>(reader_threads(), 8);
+  cx.stage->ready(T0);
+}
+void stage_to_device(int fd, const char *path, const char *mem, uint64_t n, unsigned char *dev, ReaderCtx &cx, unsigned char &last_out) {
+  const size_t B = cx.stage->block;
+  const size_t T = std::max<size_t>(1, std::min<size_t>(cx.stage->threads, (size_t)((n + B - 1) / B)));
+  hipStream_t cs = cx.stage->copy;
+  if (!n) return;
+  unsigned char last = '\n';
+  run_threads(T, [&](size_t k) {
+    MSW_HIP(hipSetDevice(cx.device));
+    int slot = 0;
+    for (uint64_t blk = k; blk * B < n; blk += T, slot ^= 1) {
+      const uint64_t off = blk * B;
+      const size_t len = (size_t)std::min<uint64_t>(B, n - off);
+      hipEvent_t e = cx.stage->ev[2 * k + slot];
+      MSW_HIP(hipEventSynchronize(e));  // the copy that last read this sub-buffer is done (never recorded: returns at once)
+      char *dst = cx.stage->sub(k, slot);
+      if (!mem) {
+        size_t got_all = 0;
+        while (got_all < len) {
+          const ssize_t got = pread(fd, dst + got_all, len - got_all, (off_t)(off + got_all));
+          if (got <= 0) throw Fail(std::string("cannot read pseudoalignment file ") + path);
+          got_all += (size_t)got;
+        }
+      } else {
+        std::memcpy(dst, mem + off, len);
+      }
+      if (off + len == n) last = (unsigned char)dst[len - 1];
+      MSW_HIP(hipMemcpyAsync(dev + off, dst, len, hipMemcpyHostToDevice, cs));
+      MSW_HIP(hipEventRecord(e, cs));
+    }
+  });
+  last_out = last;
+}
+bool upload_gzip_device(int fd, const char *path, uint64_t n, ReaderCtx &cx, DevText &t);  // host_inflate.inc
 void upload_text(const char *path, ReaderCtx &cx, DevText &t) {
   const int fd = open(path, O_RDONLY);
   if (fd < 0) throw Fail(std::string("cannot open pseudoalignment file ") + path);
@@ -133,50 +176,25 @@ void upload_text(const char *path, ReaderCtx &cx, DevText &t) {
   (void)got_magic;
   const bool plain = !(magic[0] == 0x1f && magic[1] == 0x8b) && !(magic[0] == 'B' && magic[1] == 'Z' && magic[2] == 'h') &&
                      !(magic[0] == 0xFD && magic[1] == '7' && magic[2] == 'z' && magic[3] == 'X' && magic[4] == 'Z');
+  stager_ready(cx);
+  // a gzip file goes to the device compressed and is inflated there (host_inflate.inc); where that result cannot be
+  // vouched for, the host path below stands
+  if (magic[0] == 0x1f && magic[1] == 0x8b && cx.inf && upload_gzip_device(fd, path, (uint64_t)sb.st_size, cx, t)) return;
+  if (plain && cx.inf) {
+    msw_inflate_info info = {};
+    info.text_bytes = (uint64_t)sb.st_size;
+    cx.inf->last.push_back(info);
+  }
   FileText ft;
   if (!plain) slurp_text(path, ft);  // (inflates gzip; names bzip2 / xz as unsupported)
   const uint64_t n = t.n = plain ? (uint64_t)sb.st_size : (uint64_t)ft.size;
-  // (reader threads: beyond ~8 the page-cache copies of these hosts stop scaling and only contend; MSWEEP_READER_THREADS
-  // decides when set)
-  const size_t T0 = getenv("MSWEEP_READER_THREADS") ? reader_threads() : std::min<size_t>(reader_threads(), 8);
-  cx.stage->ready(T0);
-  const size_t B = cx.stage->block;
-  const size_t T = std::max<size_t>(1, std::min<size_t>(cx.stage->threads, (size_t)((n + B - 1) / B)));
   hipStream_t cs = cx.stage->copy;
   if (!t.done) MSW_HIP(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
   const uint64_t padded = (n + kTileBytes - 1) / kTileBytes * kTileBytes + kTileBytes;
   t.txt.alloc(padded);
   MSW_HIP(hipMemsetAsync(t.txt.p + n, '\n', padded - n, cs));
   t.last = '\n';
-  if (n) {
-    unsigned char *dev = t.txt.p;
-    unsigned char last = '\n';
-    run_threads(T, [&](size_t k) {
-      MSW_HIP(hipSetDevice(cx.device));
-      int slot = 0;
-      for (uint64_t blk = k; blk * B < n; blk += T, slot ^= 1) {
-        const uint64_t off = blk * B;
-        const size_t len = (size_t)std::min<uint64_t>(B, n - off);
-        hipEvent_t e = cx.stage->ev[2 * k + slot];
-        MSW_HIP(hipEventSynchronize(e));  // the copy that last read this sub-buffer is done (never recorded: returns at once)
-        char *dst = cx.stage->sub(k, slot);
-        if (plain) {
-          size_t got_all = 0;
-          while (got_all < len) {
-            const ssize_t got = pread(fd, dst + got_all, len - got_all, (off_t)(off + got_all));
-            if (got <= 0) throw Fail(std::string("cannot read pseudoalignment file ") + path);
-            got_all += (size_t)got;
-          }
-        } else {
-          std::memcpy(dst, ft.data + off, len);
-        }
-        if (off + len == n) last = (unsigned char)dst[len - 1];
-        MSW_HIP(hipMemcpyAsync(dev + off, dst, len, hipMemcpyHostToDevice, cs));
-        MSW_HIP(hipEventRecord(e, cs));
-      }
-    });
-    t.last = last;
-  }
+  stage_to_device(fd, path, plain ? nullptr : ft.data, n, t.txt.p, cx, t.last);
   MSW_HIP(hipEventRecord(t.done, cs));
 }
 

@@ -40,6 +40,7 @@
 #include "bin_kernels.hpp"
 #include "text_kernels.hpp"
 #include "deflate_kernels.hpp"
+#include "inflate_kernels.hpp"
 
 using namespace msw;
 
@@ -242,6 +243,21 @@ struct GzState {
   }
 };
 
+// ---- gzip input inflated on the device: what its calls keep on the handle (host_inflate.inc) -------------------------------
+struct InflateState {
+  DevBuf<uint32_t> pow8;   // x^(8 2^j) mod P for k_gz_crc
+  uint32_t pow8_host[40] = {};
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // pairs around the probe and around
+                                                                                                 // pass (a) + scan; chain, pass (b), CRC in a row
+  std::vector<msw_inflate_info> last;  // per file of the last msw_alignment_read_device
+  PinnedBuf pinned{"msw_core_inflate_gzip", "the text"};
+  std::vector<char> host_text;  // ... or the host path's
+  ~InflateState() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -260,6 +276,7 @@ struct msw_core {
   DevBuf<uint32_t> iperm;  // original EC index -> permuted position (gamma blocks; built on first use)
   TextState text;
   GzState gz;
+  InflateState inf;
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
   // ---- bootstrap -------------------------------------------------------------------------
@@ -1052,6 +1069,7 @@ struct StageTimer {
 #include "host_compress.inc"
 #include "host_alignment.inc"
 #include "host_reader.inc"
+#include "host_inflate.inc"
 #include "host_bin.inc"
 #include "host_text.inc"
 #include "host_gzip.inc"
@@ -1174,6 +1192,8 @@ int msw_alignment_read_device(msw_handle h, const char *const *paths, size_t n_p
     MSW_HIP(hipStreamSynchronize(h->stream));
     h->reader_pool.recycle();  // (blocks the previous read handed back: nothing of it is in flight any more)
     ReaderCtx cx(h->stream, h->n_cu, &h->text_stage, &h->reader_pool, h->device);
+    cx.inf = &h->inf;
+    h->inf.last.clear();
     bool fits = true;
     {  // ~5 bytes of device memory per byte of text (measured: 10 GB at cfg3's 2.09 GB, 45 GB at 9.5 GB): a text that
        // would not fit beside what the device already holds goes to the host reader
@@ -1282,6 +1302,16 @@ int msw_core_text_block(msw_handle h, int what, size_t ec_begin, size_t ec_end, 
 
 int msw_core_format_g6(msw_handle h, const double *x, size_t n, const char **text_out, size_t *len_out, size_t *n_host_out) {
   return guarded(h, [&] { format_g6_impl(h, x, n, text_out, len_out, n_host_out); });
+}
+
+// ---- gzip input inflated on the device: the test and diagnostic entry, and the report of the last read --------------------
+int msw_core_inflate_gzip(msw_handle h, const uint8_t *gz, size_t n, size_t chunk_bytes, const uint8_t **text_out, size_t *len_out,
+                          msw_inflate_info *info) {
+  return guarded(h, [&] { inflate_gzip_impl(h, gz, n, chunk_bytes, text_out, len_out, info); });
+}
+
+int msw_alignment_last_inflate(msw_handle h, msw_inflate_info *info, size_t max_files, size_t *n_files) {
+  return guarded(h, [&] { last_inflate_impl(h, info, max_files, n_files); });
 }
 
 // ---- --compress z (src/OutfileDesignator.cpp:30-37) -----------------------------------------------------------------------
