@@ -411,7 +411,18 @@ int msw_alignment_read_device(msw_handle h, const char *const *paths, size_t n_p
  * kernels read it.  The member's trailer is the guarantee: the device's text is used only when its CRC-32 and length are
  * the ones the file promises; otherwise -- and for several members, trailing bytes, a header the parser does not take,
  * a payload that does not fit, a stream with too few block starts for the device to pay -- zlib inflates the same file on the host, result and messages as before.
- * MSWEEP_HOST_INFLATE=1 in the environment (developer switch, read at the call) forces the host path. */
+ * MSWEEP_HOST_INFLATE=1 in the environment (developer switch, read at the call) forces the host path.
+ * BGZF files (bgzip, htslib: gzip files of many small members, each stating its compressed length in the 'BC' subfield
+ * of its header and CRC-32 and length of at most 64 KiB of text in its trailer) take a shorter way
+ * (msweep_amd/csrc/host_inflate_members.inc): headers and trailers are walked on the host, which gives every member's
+ * payload and its offset in the text; one kernel decodes the members side by side, a wavefront each, and checks each
+ * against its own trailer.  n_members counts them (the empty ones too); n_chunks = n_starts = n_members, chunk_bytes
+ * = 0, payload_bytes = the sum of the members' DEFLATE bytes, write_ms = the decode with the check fused into it, and
+ * probe_ms, window_ms, chain_ms, crc_ms = 0.  A file that starts with such a member and does not walk to its end member
+ * by member (a plain member among them, a damaged length, trailing bytes) is the host's with the reason "header"; a
+ * member that fails its check is the host's too (reasons 4, 5, 6).  Files of several members that do not declare their
+ * lengths (cat a.gz b.gz) stay on the host: reason 6, as before.  On the single-member path and for plain files
+ * n_members is 0. */
 typedef struct msw_inflate_info {
   uint64_t payload_bytes, text_bytes;
   uint32_t chunk_bytes, n_chunks, n_starts;   /* chunks that begin at a block start the probe found (chunk 0 included) */
@@ -420,6 +431,8 @@ typedef struct msw_inflate_info {
                                                * 6 trailing bytes, 7 memory, 8 long span (a stretch between two block
                                                * starts too long for one wavefront to pay: fixed-Huffman or stored
                                                * streams, one very long block) */
+  uint32_t n_members;                         /* BGZF: the members walked and decoded one wavefront each; 0 otherwise
+                                               * (fills what was padding: size and every other offset are unchanged) */
   double kernel_ms;                           /* events on the handle's stream: probe through CRC */
   double upload_ms;                           /* host clock: the compressed bytes to the device (files only) */
   double probe_ms, window_ms, chain_ms, write_ms, crc_ms; /* the parts of kernel_ms: probe, pass (a) with the scan, window

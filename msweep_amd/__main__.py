@@ -319,6 +319,8 @@ def main(argv=None):
                 for path, info in zip(files, core.last_inflate()):
                     if info["payload_bytes"] or info["fallback_reason"]:
                         how = "the device" if info["on_device"] else f"the host ({info['reason']})"
+                        if info["on_device"] and info["n_members"]:
+                            how += f" ({info['n_members']} BGZF members)"
                         sys.stderr.write(f"note: {path}: gzip input inflated on {how}\n")
     except (RuntimeError, OSError, MswError) as ex:
         sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")

@@ -51,7 +51,8 @@ class MswError(RuntimeError):
 class InflateInfo(C.Structure):
     """msw_inflate_info: how a gzip input was inflated (Core.inflate_gzip, Core.last_inflate)"""
     _fields_ = [("payload_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("chunk_bytes", C.c_uint32), ("n_chunks", C.c_uint32),
-                ("n_starts", C.c_uint32), ("on_device", C.c_int32), ("fallback_reason", C.c_int32), ("kernel_ms", C.c_double),
+                ("n_starts", C.c_uint32), ("on_device", C.c_int32), ("fallback_reason", C.c_int32), ("n_members", C.c_uint32),
+                ("kernel_ms", C.c_double),
                 ("upload_ms", C.c_double), ("probe_ms", C.c_double), ("window_ms", C.c_double), ("chain_ms", C.c_double),
                 ("write_ms", C.c_double), ("crc_ms", C.c_double)]
 

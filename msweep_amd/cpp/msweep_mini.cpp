@@ -596,7 +596,8 @@ int main(int argc, char **argv) {
           for (size_t i = 0; i < std::min(n_info, info.size()); ++i) {
             if (!info[i].payload_bytes && !info[i].fallback_reason) continue;
             std::cerr << "note: " << paths[i] << ": gzip input inflated on ";
-            if (info[i].on_device) std::cerr << "the device\n";
+            if (info[i].on_device && info[i].n_members) std::cerr << "the device (" << info[i].n_members << " BGZF members)\n";
+            else if (info[i].on_device) std::cerr << "the device\n";
             else std::cerr << "the host (" << why[info[i].fallback_reason >= 0 && info[i].fallback_reason < 9 ? info[i].fallback_reason : 0] << ")\n";
           }
       }

@@ -9,9 +9,15 @@
 // pay (inflate_max_span) -- the host path stands, result and messages unchanged: zlib on
 // one thread (slurp_text of host_alignment.inc).  MSWEEP_HOST_INFLATE=1 (developer switch, read at the call) forces it;
 // MSWEEP_INFLATE_CHUNK=n (developer switch) sets the bytes of payload per chunk.
+// A file whose first member declares its own length (BGZF) takes host_inflate_members.inc's way instead: one decode per
+// member, no probe, windows or chain; the reasons and the host path behind it are the same.
 namespace {
 
 void pinned_reserve(PinnedBuf &B, size_t need, size_t keep);  // host_text.inc
+// files whose first member declares its length (BGZF): host_inflate_members.inc
+bool first_member_declares_length(const uint8_t *head, uint64_t avail);
+int32_t upload_members_device(int fd, const char *path, uint64_t n, ReaderCtx &cx, DevText &t, msw_inflate_info &info);
+int32_t inflate_members_bytes(msw_core *h, const uint8_t *gz, size_t n, const uint8_t **text_out, size_t *len_out, msw_inflate_info &info);
 
 struct OwnerBytes {
   __host__ __device__ uint64_t operator()(const InfOwner &o) const { return o.bytes; }
@@ -206,6 +212,8 @@ bool upload_gzip_device(int fd, const char *path, uint64_t n, ReaderCtx &cx, Dev
       m = infl::parse_member(head.data(), head.size(), n, trailer);
     if (!m.ok) {
       why = infl::kWhyHeader;
+    } else if (first_member_declares_length(head.data(), head.size())) {
+      why = upload_members_device(fd, path, n, cx, t, info);
     } else {
       const auto t0 = std::chrono::steady_clock::now();
       RBuf<uint32_t> gz(cx);
@@ -296,6 +304,8 @@ void inflate_gzip_impl(msw_core *h, const uint8_t *gz, size_t n, size_t chunk_by
     why = infl::kWhyForced;
   } else if (!m.ok) {
     why = infl::kWhyHeader;
+  } else if (first_member_declares_length(gz, n)) {
+    why = inflate_members_bytes(h, gz, n, text_out, &len, info);
   } else {
     ReaderCtx cx(h->stream, h->n_cu, &h->text_stage, &h->reader_pool, h->device);
     cx.inf = &S;

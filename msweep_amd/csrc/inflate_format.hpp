@@ -24,6 +24,9 @@
 #include <cstring>
 #include <vector>
 #endif
+// (the walk over a file of members is host code under either compiler)
+#include <cstring>
+#include <vector>
 
 namespace msw {
 namespace infl {
@@ -552,6 +555,120 @@ MSW_DF_HD inline OwnerEnd inflate_owner(const Stream &s, uint64_t start, uint64_
 // window k (markers) read through the resolved window k - 1
 MSW_DF_HD inline uint8_t resolve_entry(uint16_t e, const uint8_t *prev) { return (e & kMarker) ? prev[e & kWinMask] : (uint8_t)e; }
 
+// ---- files of members that declare their own lengths: BGZF (htslib's blocked gzip, what bgzip writes) -------------------
+// A BGZF member's header carries an extra subfield 'B' 'C' of two bytes, BSIZE = the member's length - 1; its trailer
+// states CRC-32 and length of at most 64 KiB of text; it starts with an empty window.  So a walk over headers and trailers
+// alone gives every member's payload and its place in the text before anything is decoded: one decode per member, side
+// by side, checked per member (inflate_member_kernels.hpp; members_reference below runs the same steps on one thread).
+constexpr uint32_t kMemberMaxText = 65536;
+struct MemberEntry {
+  uint64_t first_bit, end_bit;  // the payload's first bit; the bit behind its last byte (the trailer's first bit)
+  uint64_t text_off;            // exclusive prefix sum of the members' ISIZE
+  uint32_t crc, isize;          // the trailer
+};
+// BSIZE of the header in p[0 .. avail): magic, CM 8, FEXTRA, and the subfield 'B' 'C' of length 2 found by walking the
+// extra field's subfields, which must fill it exactly
+MSW_DF_HD inline bool member_bsize(const uint8_t *p, uint64_t avail, uint32_t *bsize) {
+  if (avail < 12 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4) || (p[3] & 0xe0)) return false;
+  const uint64_t end = 12 + (p[10] | (uint64_t)p[11] << 8);
+  if (end > avail) return false;
+  bool found = false;
+  uint64_t at = 12;
+  while (at < end) {  // (every subfield takes at least four bytes)
+    if (at + 4 > end) return false;
+    const uint64_t slen = p[at + 2] | (uint64_t)p[at + 3] << 8;
+    if (at + 4 + slen > end) return false;
+    if (!found && p[at] == 66 && p[at + 1] == 67 && slen == 2) {
+      *bsize = p[at + 4] | (uint32_t)p[at + 5] << 8;
+      found = true;
+    }
+    at += 4 + slen;
+  }
+  return found;
+}
+// a member's stream ends at its own trailer: nothing behind it is read as payload (words from there on read as zero)
+MSW_DF_HD inline Stream member_stream(const uint32_t *w, uint64_t n_words, const MemberEntry &m) {
+  const uint64_t own = (m.end_bit + 31) / 32;
+  return Stream{w, own < n_words ? own : n_words, m.end_bit};
+}
+// what a member's decode (inflate_owner from first_bit to the final block, FinalSink with cap = ISIZE and first = true)
+// must have left, in front of the CRC: kWhyNone, or the reason the host path serves the file
+MSW_DF_HD inline int32_t member_verdict(const OwnerEnd &e, uint64_t count, const MemberEntry &m) {
+  if (e.status != kOk || !e.final) return kWhyStatus;
+  if ((e.end_bit + 7) / 8 * 8 != m.end_bit) return kWhyTrailing;  // the final block ends in the member's last payload byte
+  if (count != m.isize) return kWhyCrc;
+  return kWhyNone;
+}
+// (host code from here on, under either compiler)
+struct MemberTable {
+  std::vector<MemberEntry> members;
+  uint64_t text_bytes = 0, payload_bytes = 0;  // sum of ISIZE; sum of the DEFLATE payloads' bytes
+};
+// bytes in memory as the walk's source (a file: pread, host_inflate_members.inc)
+struct BufferFetch {
+  const uint8_t *p;
+  uint64_t n;
+  bool operator()(uint64_t off, size_t len, uint8_t *dst) const {
+    if (off > n || len > n - off) return false;
+    std::memcpy(dst, p + off, len);
+    return true;
+  }
+};
+// The member table of a file of n bytes, or false: "not BGZF".  fetch(off, len, dst) reads len bytes at off (off + len
+// <= n).  Every member must qualify -- member_bsize's header with the other optional fields as parse_member takes them,
+// BSIZE + 1 >= header + 8, the member inside the file, ISIZE <= 64 KiB -- and the walk (next member at offset + BSIZE + 1)
+// must land exactly on the end of the file: a plain member anywhere, trailing bytes or a cut last member refuse the whole
+// file.  Members of ISIZE 0 (BGZF's end-of-file marker, at the end or inside a concatenation) are ordinary members.
+// Only headers and trailers are read: a trailer and the header behind it in one fetch.
+template <class Fetch>
+inline bool walk_members(Fetch &&fetch, uint64_t n, MemberTable &T) {
+  T.members.clear();
+  T.text_bytes = T.payload_bytes = 0;
+  constexpr uint64_t kAhead = 8 + 32;  // a trailer and the usual header (18 bytes) behind it
+  std::vector<uint8_t> win((size_t)kAhead);
+  uint64_t win_off = 0, win_len = 0;
+  auto view = [&](uint64_t off, uint64_t len) -> const uint8_t * {  // (off + len <= n)
+    if (off < win_off || off + len > win_off + win_len) {
+      uint64_t want = len > kAhead ? len : kAhead;
+      if (want > n - off) want = n - off;
+      if (win.size() < want) win.resize((size_t)want);
+      if (!fetch(off, (size_t)want, win.data())) return nullptr;
+      win_off = off, win_len = want;
+    }
+    return win.data() + (off - win_off);
+  };
+  uint64_t off = 0;
+  while (off < n) {
+    if (n - off < 18 + 8) return false;
+    uint64_t avail = n - off < 32 ? n - off : 32;
+    const uint8_t *p = view(off, avail);
+    if (!p) return false;
+    if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return false;
+    // an extra field longer than the usual one, or names / a header CRC behind it: the whole header (a member is at
+    // most 64 KiB)
+    if (12 + (p[10] | (uint64_t)p[11] << 8) > avail || (p[3] & 0x1a)) {
+      avail = n - off < 65536 ? n - off : 65536;
+      if (!(p = view(off, avail))) return false;
+    }
+    uint32_t bsize = 0;
+    if (!member_bsize(p, avail, &bsize)) return false;
+    const uint64_t msize = (uint64_t)bsize + 1;
+    if (msize > n - off) return false;
+    static const uint8_t no_trailer[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const Member m = parse_member(p, avail < msize ? avail : msize, msize, no_trailer);  // (n >= 18, payload <= n - 8)
+    if (!m.ok) return false;
+    const uint8_t *tr = view(off + msize - 8, 8);  // (p is gone from here on)
+    if (!tr) return false;
+    const uint32_t crc = le32(tr), isize = le32(tr + 4);
+    if (isize > kMemberMaxText) return false;
+    T.members.push_back(MemberEntry{8 * (off + m.payload), 8 * (off + msize - 8), T.text_bytes, crc, isize});
+    T.text_bytes += isize;
+    T.payload_bytes += msize - 8 - m.payload;
+    off += msize;
+  }
+  return !T.members.empty();
+}
+
 #if !defined(__HIPCC__)
 // ---- the plain reference: the kernels' steps, one thread ----------------------------------------------------------------
 struct Reference {
@@ -656,6 +773,47 @@ inline Reference inflate_reference(const uint8_t *gz, size_t n, size_t chunk = k
   if (crc32_plain(R.text.data(), R.text.size()) != m.crc || (uint32_t)R.text.size() != m.isize) {
     R.why = kWhyCrc;
     R.text.clear();
+  }
+  return R;
+}
+
+// ---- the plain reference for a file of members: the member kernel's steps, one thread -----------------------------------
+struct MembersReference {
+  int32_t why = kWhyNone;  // kWhyNone: `text` is the file's text, every member's with its trailer's CRC-32 and length
+  std::vector<uint8_t> text;
+  uint32_t n_members = 0;
+  uint32_t bad_member = 0, bad_status = 0;  // the first member that failed, and its decode's status
+  uint64_t payload_bytes = 0;
+};
+inline MembersReference members_reference(const uint8_t *gz, size_t n) {
+  MembersReference R;
+  MemberTable T;
+  if (!walk_members(BufferFetch{gz, n}, n, T)) {
+    R.why = kWhyHeader;  // not BGZF
+    return R;
+  }
+  R.n_members = (uint32_t)T.members.size();
+  R.payload_bytes = T.payload_bytes;
+  std::vector<uint32_t> words((n + 3) / 4 + 4, 0);
+  std::memcpy(words.data(), gz, n);
+  std::vector<uint16_t> ws(kWsSize);
+  const Tables t = tables_in(ws.data());
+  std::vector<uint8_t> ring(kWindow);
+  R.text.assign(T.text_bytes, 0);
+  for (size_t k = 0; k < T.members.size(); ++k) {
+    const MemberEntry &m = T.members[k];
+    const Stream s = member_stream(words.data(), words.size(), m);
+    FinalSink sink = {ring.data(), R.text.data() + m.text_off, 0, m.isize, kOk, true, 0, 1};
+    const OwnerEnd e = inflate_owner(s, m.first_bit, kNoStart, t, sink);
+    int32_t why = member_verdict(e, sink.count, m);
+    if (why == kWhyNone && crc32_plain(R.text.data() + m.text_off, m.isize) != m.crc) why = kWhyCrc;
+    if (why != kWhyNone) {
+      R.why = why;
+      R.bad_member = (uint32_t)k;
+      R.bad_status = e.status;
+      R.text.clear();
+      return R;
+    }
   }
   return R;
 }

@@ -41,6 +41,7 @@
 #include "text_kernels.hpp"
 #include "deflate_kernels.hpp"
 #include "inflate_kernels.hpp"
+#include "inflate_member_kernels.hpp"
 
 using namespace msw;
 
@@ -1070,6 +1071,7 @@ struct StageTimer {
 #include "host_alignment.inc"
 #include "host_reader.inc"
 #include "host_inflate.inc"
+#include "host_inflate_members.inc"
 #include "host_bin.inc"
 #include "host_text.inc"
 #include "host_gzip.inc"
