@@ -449,6 +449,48 @@ int msw_core_inflate_gzip(msw_handle h, const uint8_t *gz, size_t n, size_t chun
 /* One entry per file of the last msw_alignment_read_device on h, in the order of its paths (a plain file: all zero but
  * text_bytes): which path served each strand.  At most max_files entries are written; *n_files = how many there are. */
 int msw_alignment_last_inflate(msw_handle h, msw_inflate_info *info, size_t max_files, size_t *n_files);
+
+/* ---- --read-likelihood on the device (include/Likelihood.hpp:224-253) ------------------------------------------------
+ * The file -- plain, gzip or BGZF: the same upload as msw_alignment_read_device, inflate included -- is parsed by kernels
+ * (msweep_amd/csrc/likelihood_text_kernels.hpp, host_likelihood_file.inc) and the resident likelihood is built from the
+ * staged matrix on by the code behind msw_core_set_dense_logl.  A file is SERVED or NOT SERVED.
+ * Served (served = 1, reason = 0): the handle holds exactly the state msw_core_set_dense_logl would leave from the
+ * host-parsed matrix of that file -- msw_core_get_dense_logl bit for bit, msw_core_layout_hash, msw_core_shape's nnz --,
+ * re-expressed as CSR-of-ECs or kept dense alike.
+ * Not served (served = 0, reason != 0): the call returns 0, whatever was resident before stays resident, and the caller
+ * runs its own parser, whose result or message stands.  A non-zero return is a null argument or a HIP error only.
+ * The device serves one grammar and judges no other text:
+ *   every line is  count '\t' cell ('\t' cell){n_groups - 1} '\n'   (the last line may lack its '\n');
+ *   count: 1 to 18 digits;  cell: inf, -inf, nan, -nan, or -?digits(.digits)?(e[+-]?digits)? of at most 24 bytes.
+ * Any other byte ('\r', blanks, a '+' in front of a mantissa, upper case), a blank line, another column count, an empty
+ * file, 2^32 - 1 or more lines, text and matrices that do not fit in free device memory: not served.  For the grammar
+ * served, float(), std::stod and strtod agree on the value -- with one exception: a cell that rounds to a subnormal
+ * (2.5e-320) is served with strtod's double, as float() reads it, although glibc sets ERANGE there and std::stod, hence
+ * msweep_mini's host parser, throws on it.  Cells that one IEEE operation converts exactly (Clinger's case:
+ * at most 2^53 as an integer, |decimal exponent| <= 22; msweep_amd/csrc/dec_parse.hpp) are converted by the kernels; the
+ * others -- at most 65 536 per file, n_host_cells -- by strtod on the host, their bytes fetched from the device.
+ * MSWEEP_HOST_LIKELIHOOD_FILE=1 in the environment (developer switch, read at the call): not served, reason forced. */
+#define MSW_LIKFILE_FORCED 1      /* the developer switch */
+#define MSW_LIKFILE_OPEN 2        /* the file cannot be opened or read (inflate errors included) */
+#define MSW_LIKFILE_BAD_BYTE 3    /* a byte outside the grammar */
+#define MSW_LIKFILE_BAD_TOKEN 4   /* a count or cell the grammar does not have; a cell of more than 24 bytes */
+#define MSW_LIKFILE_COLUMNS 5     /* a line without n_groups + 1 columns (blank lines, doubled tabs, n_groups = 0) */
+#define MSW_LIKFILE_EMPTY 6       /* no text */
+#define MSW_LIKFILE_HOST_CELLS 7  /* more than 65 536 cells for the host's strtod */
+#define MSW_LIKFILE_RANGE 8       /* strtod reports ERANGE and returns an infinity or zero (1e400, 1e-400) */
+#define MSW_LIKFILE_MEMORY 9      /* text plus matrices do not fit in free device memory */
+#define MSW_LIKFILE_LINES 10      /* 2^32 - 1 or more lines */
+typedef struct msw_likfile_info {
+  uint64_t text_bytes, n_ecs, n_host_cells;   /* the (inflated) text; lines; cells converted on the host */
+  int32_t served, reason;                     /* reason: 0 or MSW_LIKFILE_* */
+  double upload_ms, kernel_ms;                /* host clock: the text to the device (inflate included); events: pass 1 through the transpose */
+  msw_inflate_info inflate;                   /* the file's entry of msw_alignment_last_inflate (a plain file: text_bytes only) */
+} msw_likfile_info;
+int msw_core_set_dense_logl_file(msw_handle h, const char *path, size_t n_groups, msw_likfile_info *info);
+/* test / diagnostic entry: plain text in host memory */
+int msw_core_set_dense_logl_text(msw_handle h, const char *text, size_t n, size_t n_groups, msw_likfile_info *info);
+/* first column of the last served file: the read counts of its n_ecs lines */
+int msw_core_likfile_counts(msw_handle h, uint64_t *counts_out, size_t n_ecs);
 /* 1: the handle's arrays are device-resident (msw_alignment_read_device served the text with its kernels); 0: host
  * arrays (msw_alignment_read, or the host parser behind the device entry). */
 int msw_alignment_on_device(msw_alignment_t a);

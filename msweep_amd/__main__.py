@@ -15,7 +15,7 @@ import numpy as np
 
 from . import binning, parallel
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
-from .likelihood import from_device_alignment, from_dense
+from .likelihood import from_device_alignment, from_likelihood_file, read_likelihood_file  # noqa: F401 (read_likelihood_file: the host parser, under its name here)
 from .reference import read_reference
 from .sample import BootstrapSample, PlainSample
 
@@ -56,18 +56,6 @@ def parse(argv):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
-
-
-def read_likelihood_file(path, n_groups):
-    counts, cols = [], []
-    with open(path) as f:
-        for line in f:
-            parts = line.rstrip("\n").split("\t")
-            if len(parts) != n_groups + 1:
-                raise RuntimeError("Could not read from the likelihoods file.")
-            counts.append(int(parts[0]))
-            cols.append([float(x) for x in parts[1:]])
-    return np.array(counts, np.uint64), np.ascontiguousarray(np.array(cols).T)
 
 
 def host_text():
@@ -339,8 +327,12 @@ def main(argv=None):
         core.set_pack_schedule(a.iters >= 5)
         if a.read_likelihood:
             # --read-likelihood (include/Likelihood.hpp:224-253): "count \t L(0,j) ... L(G-1,j)" per EC
-            ec_counts, L = read_likelihood_file(a.read_likelihood, grouping.get_n_groups())
-            lik = from_dense(core, L, np.log(ec_counts.astype(np.float64)))
+            # -- parsed on the device where it serves the file (plain, gzip or BGZF), by read_likelihood_file otherwise
+            lik = from_likelihood_file(core, a.read_likelihood, grouping.get_n_groups())
+            ec_counts, info = lik.ec_counts, lik.file_info
+            if a.verbose:
+                how = f"the device ({info['n_host_cells']} cells on the host)" if info["served"] else f"the host ({info['reason_text']})"
+                sys.stderr.write(f"note: {a.read_likelihood}: likelihood file parsed on {how}\n")
             n_reads = total_reads = int(ec_counts.sum())
         else:
             if aln.n_ecs == 0:

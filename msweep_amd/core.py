@@ -38,6 +38,7 @@ EXPORTS = [
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
     "msw_core_inflate_gzip", "msw_alignment_last_inflate",
+    "msw_core_set_dense_logl_file", "msw_core_set_dense_logl_text", "msw_core_likfile_counts",
 ]
 
 # msw_inflate_info.fallback_reason
@@ -59,6 +60,23 @@ class InflateInfo(C.Structure):
     def as_dict(self):
         d = {name: getattr(self, name) for name, _ in self._fields_}
         d["reason"] = INFLATE_REASONS[self.fallback_reason] if 0 <= self.fallback_reason < len(INFLATE_REASONS) else "?"
+        return d
+
+
+# msw_likfile_info.reason (include/msweep_core.h: MSW_LIKFILE_*)
+LIKFILE_REASONS = ("none", "forced", "open / read", "bad byte", "bad token", "column count", "empty", "too many host cells",
+                   "range error", "memory", "too many lines")
+
+
+class LikFileInfo(C.Structure):
+    """msw_likfile_info: whether the device served a --read-likelihood file (Core.set_dense_logl_file), and how"""
+    _fields_ = [("text_bytes", C.c_uint64), ("n_ecs", C.c_uint64), ("n_host_cells", C.c_uint64), ("served", C.c_int32),
+                ("reason", C.c_int32), ("upload_ms", C.c_double), ("kernel_ms", C.c_double), ("inflate", InflateInfo)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "inflate"}
+        d["inflate"] = self.inflate.as_dict()
+        d["reason_text"] = LIKFILE_REASONS[self.reason] if 0 <= self.reason < len(LIKFILE_REASONS) else "?"
         return d
 
 
@@ -133,6 +151,9 @@ def load_library():
     L.msw_core_version.restype = C.c_char_p
     L.msw_core_set_dense_logl.argtypes = [vp, vp, sz, sz, sz]
     L.msw_core_set_csr.argtypes = [vp, vp, vp, vp, vp, sz, dp, sz, sz]
+    L.msw_core_set_dense_logl_file.argtypes = [vp, C.c_char_p, sz, C.POINTER(LikFileInfo)]
+    L.msw_core_set_dense_logl_text.argtypes = [vp, vp, sz, sz, C.POINTER(LikFileInfo)]
+    L.msw_core_likfile_counts.argtypes = [vp, vp, sz]
     L.msw_core_build_likelihood.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, vp, dp, dp, dp, sz,
                                             C.POINTER(sz), vp, vp]
     L.msw_core_get_dense_logl.argtypes = [vp, vp, sz]
@@ -339,7 +360,32 @@ class Core:
         if logl.strides[1] != 8 or logl.strides[0] % 8 or logl.strides[0] < 8 * logl.shape[1]:
             logl = np.ascontiguousarray(logl)
         G, E = logl.shape
-        self._check(self._L.msw_core_set_dense_logl(self._h, _ptr(logl), G, E, logl.strides[0] // 8 if G else E))
+        # (a single row's stride is arbitrary in numpy: its leading dimension is the row itself)
+        self._check(self._L.msw_core_set_dense_logl(self._h, _ptr(logl), G, E, logl.strides[0] // 8 if G > 1 else E))
+
+    def _likfile_result(self, info):
+        d = info.as_dict()
+        counts = None
+        if d["served"]:
+            counts = np.empty(d["n_ecs"], np.uint64)
+            self._check(self._L.msw_core_likfile_counts(self._h, _ptr(counts), len(counts)))
+        return d, counts
+
+    def set_dense_logl_file(self, path, n_groups):
+        """--read-likelihood on the device (msw_core_set_dense_logl_file): (info, counts).  info["served"] = 1: the file --
+        plain, gzip or BGZF -- was parsed by the kernels, the handle holds what set_dense_logl would leave from its matrix and
+        counts is its first column (uint64).  served = 0: nothing changed on the handle, counts is None and info["reason_text"]
+        says why; the caller parses the file itself."""
+        info = LikFileInfo()
+        self._check(self._L.msw_core_set_dense_logl_file(self._h, os.fsencode(path), int(n_groups), C.byref(info)))
+        return self._likfile_result(info)
+
+    def set_dense_logl_text(self, text, n_groups):
+        """set_dense_logl_file on plain text in host memory (bytes): the parser's test and diagnostic entry"""
+        text = bytes(text)
+        info = LikFileInfo()
+        self._check(self._L.msw_core_set_dense_logl_text(self._h, text if text else None, len(text), int(n_groups), C.byref(info)))
+        return self._likfile_result(info)
 
     def set_csr(self, rowptr, grp, cnt, lut, logzi, n_groups):
         rowptr = _arr(rowptr, np.uint64)

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <map>
 #include <random>
 #include <sstream>
@@ -228,10 +229,26 @@ std::string g6(double x) {
   return buf;
 }
 
-// LL_WOR21::from_file (include/Likelihood.hpp:224-253): one line per equivalence class, `count \t L(0,j) ... L(G-1,j)`
-void read_likelihood_file(const std::string &path, size_t G, std::vector<uint64_t> &counts, std::vector<double> &L) {
-  std::ifstream in(path);
-  if (!in) throw std::runtime_error("Could not read from the likelihoods file.");
+// LL_WOR21::from_file (include/Likelihood.hpp:224-253): one line per equivalence class, `count \t L(0,j) ... L(G-1,j)`.
+// The host parser: main() asks the device first (msw_core_set_dense_logl_file) and comes here for what it does not serve.
+// A file that starts with the gzip magic is inflated through the library (msw_core_inflate_gzip: the kernels, or zlib).
+void read_likelihood_file(msw_handle h, const std::string &path, size_t G, std::vector<uint64_t> &counts, std::vector<double> &L) {
+  std::ifstream file(path, std::ios::binary);
+  if (!file) throw std::runtime_error("Could not read from the likelihoods file.");
+  std::istringstream inflated;
+  const bool gz = file.get() == 0x1f && file.get() == 0x8b;
+  file.clear();
+  file.seekg(0);
+  if (gz) {
+    const std::string bytes((std::istreambuf_iterator<char>(file)), std::istreambuf_iterator<char>());
+    const uint8_t *text = nullptr;
+    size_t len = 0;
+    msw_inflate_info info;
+    if (msw_core_inflate_gzip(h, reinterpret_cast<const uint8_t *>(bytes.data()), bytes.size(), 0, &text, &len, &info))
+      throw std::runtime_error("Could not read from the likelihoods file.");
+    inflated.str(std::string(reinterpret_cast<const char *>(text), len));
+  }
+  std::istream &in = gz ? static_cast<std::istream &>(inflated) : file;
   std::vector<std::vector<double>> cols;
   std::string line;
   while (std::getline(in, line)) {
@@ -625,11 +642,27 @@ int main(int argc, char **argv) {
     check(h, msw_core_set_pack_schedule(h, a.iters >= 5 ? 1 : 0));
     if (!a.read_likelihood.empty()) {
       // --read-likelihood (include/Likelihood.hpp:224-253): the dense matrix of a file through the dense boundary
-      std::vector<double> L;
-      read_likelihood_file(a.read_likelihood, G, ec_counts, L);
-      n_ecs = ec_counts.size();
-      if (n_ecs == 0) throw std::runtime_error("Could not read from the likelihoods file.");
-      check(h, msw_core_set_dense_logl(h, L.data(), G, n_ecs, n_ecs));
+      // -- parsed on the device where it serves the file (plain, gzip or BGZF), by read_likelihood_file otherwise
+      msw_likfile_info lf;
+      check(h, msw_core_set_dense_logl_file(h, a.read_likelihood.c_str(), G, &lf));
+      if (a.verbose) {
+        static const char *const why[] = {"none", "forced", "open / read", "bad byte", "bad token", "column count", "empty",
+                                          "too many host cells", "range error", "memory", "too many lines"};
+        std::cerr << "note: " << a.read_likelihood << ": likelihood file parsed on ";
+        if (lf.served) std::cerr << "the device (" << lf.n_host_cells << " cells on the host)\n";
+        else std::cerr << "the host (" << why[lf.reason >= 0 && lf.reason < 11 ? lf.reason : 0] << ")\n";
+      }
+      if (lf.served) {
+        n_ecs = (size_t)lf.n_ecs;
+        ec_counts.resize(n_ecs);
+        check(h, msw_core_likfile_counts(h, ec_counts.data(), n_ecs));
+      } else {
+        std::vector<double> L;
+        read_likelihood_file(h, a.read_likelihood, G, ec_counts, L);
+        n_ecs = ec_counts.size();
+        if (n_ecs == 0) throw std::runtime_error("Could not read from the likelihoods file.");
+        check(h, msw_core_set_dense_logl(h, L.data(), G, n_ecs, n_ecs));
+      }
       n_kept = G;
       for (uint64_t c : ec_counts) {
         logc_file.push_back(std::log((double)c));

@@ -39,8 +39,11 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <fstream>
+#include <iterator>
 #include <memory>
 #include <ostream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -176,7 +179,74 @@ class DeviceLikelihood {
     mask_.assign(mask.begin(), mask.end());
     built_ = true;
   }
-  const std::vector<uint64_t> &ec_counts() const { return ec_counts_; }   // reads per class (build_from_files)
+  // LL_WOR21::from_file (include/Likelihood.hpp:224-253), the mirror of --read-likelihood: one line per class,
+  // `count \t L(0,j) ... L(n_groups-1,j)`, plain, gzip or BGZF.  The device parses what it serves
+  // (msw_core_set_dense_logl_file: a strict grammar); any other text is read here, cell by cell, and uploaded through
+  // msw_core_set_dense_logl -- the same resident likelihood either way.  Afterwards ec_counts() / log_counts() hold the
+  // first column and its logarithms; parsed_on_device() tells which path served.  A file that cannot be opened, or a line
+  // with another column count, throws the reference's message.
+  void from_file(const std::string &path, size_t n_groups) {
+    static const char *const kMsg = "Could not read from the likelihoods file.";
+    msw_likfile_info lf;
+    check(h_, msw_core_set_dense_logl_file(h_, path.c_str(), n_groups, &lf));
+    file_info_ = lf;
+    if (lf.served) {
+      ec_counts_.assign((size_t)lf.n_ecs, 0);
+      check(h_, msw_core_likfile_counts(h_, ec_counts_.data(), ec_counts_.size()));
+    } else {
+      std::ifstream file(path, std::ios::binary);
+      if (!file) throw std::runtime_error(kMsg);
+      std::string text((std::istreambuf_iterator<char>(file)), std::istreambuf_iterator<char>());
+      if (text.size() >= 2 && (unsigned char)text[0] == 0x1f && (unsigned char)text[1] == 0x8b) {
+        const uint8_t *out = nullptr;
+        size_t len = 0;
+        msw_inflate_info info;
+        if (msw_core_inflate_gzip(h_, reinterpret_cast<const uint8_t *>(text.data()), text.size(), 0, &out, &len, &info))
+          throw std::runtime_error(kMsg);
+        text.assign(reinterpret_cast<const char *>(out), len);
+      }
+      // the host parser: strtod per cell, as msweep_mini's; anything it does not take is the reference's message
+      ec_counts_.clear();
+      std::vector<double> cells;  // [E][n_groups]
+      std::istringstream in(text);
+      std::string line, tok;
+      while (std::getline(in, line)) {
+        std::istringstream fields(line);
+        size_t cols = 0;
+        while (std::getline(fields, tok, '\t')) {
+          char *end = nullptr;
+          if (tok.empty()) throw std::runtime_error(kMsg);
+          if (cols == 0) {
+            if (tok.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error(kMsg);
+            ec_counts_.push_back(std::strtoull(tok.c_str(), &end, 10));
+          } else {
+            cells.push_back(std::strtod(tok.c_str(), &end));
+          }
+          if (*end) throw std::runtime_error(kMsg);
+          ++cols;
+        }
+        if (cols != n_groups + 1) throw std::runtime_error(kMsg);
+      }
+      const size_t E = ec_counts_.size();
+      if (E == 0) throw std::runtime_error(kMsg);
+      std::vector<double> L(n_groups * E);
+      for (size_t j = 0; j < E; ++j)
+        for (size_t g = 0; g < n_groups; ++g) L[g * E + j] = cells[j * n_groups + g];
+      check(h_, msw_core_set_dense_logl(h_, L.data(), n_groups, E, E));
+    }
+    logc_.resize(ec_counts_.size());
+    n_reads_ = n_aligned_ = 0;
+    for (size_t j = 0; j < ec_counts_.size(); ++j) {
+      logc_[j] = std::log((double)ec_counts_[j]);
+      n_reads_ += ec_counts_[j];
+    }
+    n_aligned_ = n_reads_;
+    mask_.assign(n_groups, true);
+    built_ = false;
+  }
+  bool parsed_on_device() const { return file_info_.served != 0; }   // the last from_file
+  const msw_likfile_info &file_info() const { return file_info_; }
+  const std::vector<uint64_t> &ec_counts() const { return ec_counts_; }   // reads per class (build_from_files, from_file)
   size_t n_reads() const { return n_reads_; }
   size_t n_aligned() const { return n_aligned_; }
   const std::vector<double> &log_counts() const { return logc_; }          // Likelihood::log_counts()
@@ -200,6 +270,7 @@ class DeviceLikelihood {
   size_t n_reads_ = 0, n_aligned_ = 0;
   std::vector<bool> mask_;
   bool built_ = false;
+  msw_likfile_info file_info_ = {};
 };
 
 struct Estimate {

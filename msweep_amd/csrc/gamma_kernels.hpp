@@ -68,8 +68,10 @@ __global__ __launch_bounds__(256) void k_gamma_block(SellDev S, const uint32_t *
     const uint32_t p = iperm[j];
     const double lse = normalise ? gamma_lse<ENC>(S, p, a, tref, u, M, U, p0) : 0.0;
     double *col = out + (j - e0);
-    for (uint32_t g = 0; g < S.n_groups; ++g) col[(size_t)g * ld] = gamma_cell(a, logzi, u[g], lse);
-    for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { col[(size_t)g * ld] = gamma_cell(a, T, u[g], lse); });
+    // (the likelihood itself is the stored value as it is: 1 * T + 0 - 0 would turn a cell of -0 into +0, and
+    // msw_core_get_dense_logl returns its input bit for bit)
+    for (uint32_t g = 0; g < S.n_groups; ++g) col[(size_t)g * ld] = normalise ? gamma_cell(a, logzi, u[g], lse) : logzi;
+    for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { col[(size_t)g * ld] = normalise ? gamma_cell(a, T, u[g], lse) : T; });
   }
 }
 
@@ -89,7 +91,8 @@ __global__ __launch_bounds__(256) void k_gamma_dense(const double *Lt, int G, ui
     for (int g = 0; g < G; ++g) Z += exp(a * row[g] + u[g] - m);
     lse = m + log(Z);
   }
-  for (int g = g_begin; g < g_end; ++g) out[(size_t)(g - g_begin) * ld + j] = a * row[g] + u[g] - lse;
+  // (sub_lse = 0 is the likelihood itself, (a, u) = (1, 0): the stored bits, -0 included)
+  for (int g = g_begin; g < g_end; ++g) out[(size_t)(g - g_begin) * ld + j] = sub_lse ? a * row[g] + u[g] - lse : row[g];
 }
 
 }  // namespace msw

@@ -10,7 +10,8 @@ constexpr uint32_t kCompressMaxValues = 1u << 24;  // distinct listed values (ea
 constexpr uint32_t kCompressShared = 1u << 16;     // up to here equal values share a slot (tables can sit in LDS)
 constexpr size_t kCompressSample = 4096;
 
-// stage: the matrix on the device, [G][E] contiguous.  True = h now holds the CSR flavour.
+// stage: the matrix on the device, [G][E] contiguous; Lm: the same matrix on the host, or null (the background sample
+// is then read from the stage).  True = h now holds the CSR flavour.
 // force: the matrix has more groups than the dense sweeps take (dense_kernels.hpp: 8192) -- it is re-expressed
 // whatever its shape (most frequent sampled value as the background, every other cell listed with a slot of its
 // own), up to 2^28 listed cells.
@@ -25,12 +26,28 @@ bool compress_dense(msw_core *h, const double *Lm, size_t ld, const double *stag
     std::unordered_map<uint64_t, uint32_t> seen;
     const size_t cells = G * E, n = std::min(cells, kCompressSample);
     uint64_t x = 0x9E3779B97F4A7C15ull;
-    uint32_t best = 0;
+    // the sampled cells, as indices into the [G][E] stage, and their bits: from the host matrix, or -- Lm null, a matrix
+    // that never was on the host (host_likelihood_file.inc) -- the same cells fetched from the stage (<= 32 KB)
+    std::vector<uint64_t> at(n), val(n);
     for (size_t i = 0; i < n; ++i) {
       x = x * 6364136223846793005ull + 1442695040888963407ull;
-      const size_t c = cells <= kCompressSample ? i : (size_t)((x >> 11) % cells);
-      uint64_t v;
-      std::memcpy(&v, &Lm[(c / E) * ld + c % E], sizeof v);
+      at[i] = cells <= kCompressSample ? i : (size_t)((x >> 11) % cells);
+    }
+    if (Lm) {
+      for (size_t i = 0; i < n; ++i) std::memcpy(&val[i], &Lm[(at[i] / E) * ld + at[i] % E], sizeof(uint64_t));
+    } else {
+      DevBuf<uint64_t> d_at;
+      DevBuf<double> d_val;
+      d_at.upload(at.data(), n, h->stream);
+      d_val.alloc(n);
+      hipLaunchKernelGGL(k_lik_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, stage, d_at.p, (uint32_t)n, d_val.p);
+      MSW_HIP(hipGetLastError());
+      MSW_HIP(hipMemcpyAsync(val.data(), d_val.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+      MSW_HIP(hipStreamSynchronize(h->stream));
+    }
+    uint32_t best = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t v = val[i];
       const uint32_t k = ++seen[v];
       if (k > best) {
         best = k;

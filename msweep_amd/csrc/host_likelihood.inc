@@ -521,21 +521,14 @@ void set_csr_impl(msw_core *h, const uint64_t *rowptr, const uint32_t *grp, cons
   tm.mark("set_csr: pack (total)");
 }
 
-void set_dense_impl(msw_core *h, const double *Lm, size_t G, size_t E, size_t ld) {
+// From the staged [G][E] device matrix on: what msw_core_set_dense_logl (a host matrix, staged below) and
+// msw_core_set_dense_logl_file (a matrix parsed on the device, host_likelihood_file.inc: Lm = null) share.  The caller has
+// called reset_likelihood.
+void dense_from_stage(msw_core *h, const double *Lm, size_t ld, const double *stage, size_t G, size_t E) {
   Resident &L = h->lik;
-  if (!Lm) throw Fail("msw_core_set_dense_logl: null matrix");
-  if (G == 0 || E == 0) throw Fail("msw_core_set_dense_logl: empty likelihood");
-  if (ld < E) throw Fail("msw_core_set_dense_logl: ld < n_ecs");
-  if (E >= 0xffffffffull) throw Fail("msw_core_set_dense_logl: n_ecs exceeds 32 bits");
-  reset_likelihood(h);
-  // rows = groups, staged as they come; then either re-expressed as CSR-of-ECs (host_compress.inc:
-  // the reference's matrices are a background value plus few listed cells) ...
-  DevBuf<double> stage;
-  stage.alloc(G * E);
-  MSW_HIP(hipMemcpy2DAsync(stage.p, E * sizeof(double), Lm, ld * sizeof(double), E * sizeof(double), G,
-                           hipMemcpyHostToDevice, h->stream));
-  // (more groups than the dense sweeps take, 8192: re-expressed whatever its shape)
-  if (compress_dense(h, Lm, ld, stage.p, G, E, G > 8192)) return;
+  // either re-expressed as CSR-of-ECs (host_compress.inc: the reference's matrices are a background value plus few
+  // listed cells; more groups than the dense sweeps take, 8192: re-expressed whatever its shape) ...
+  if (compress_dense(h, Lm, ld, stage, G, E, G > 8192)) return;
   // ... or kept dense, EC-major
   L.G = (uint32_t)G;
   L.E = (uint32_t)E;
@@ -546,7 +539,7 @@ void set_dense_impl(msw_core *h, const double *Lm, size_t G, size_t E, size_t ld
   L.nreg = nreg;
   L.Lt.alloc(G * E);
   dim3 grid((unsigned)((E + 63) / 64), (unsigned)((G + 63) / 64));
-  hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, h->stream, stage.p, E, (int)G, (uint32_t)E, L.Lt.p);
+  hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, h->stream, stage, E, (int)G, (uint32_t)E, L.Lt.p);
   MSW_HIP(hipGetLastError());
   MSW_HIP(hipStreamSynchronize(h->stream));
   L.lut.alloc(1);
@@ -558,6 +551,20 @@ void set_dense_impl(msw_core *h, const double *Lm, size_t G, size_t E, size_t ld
   L.flavor = 1;
   alloc_solve_state(L, h->solver);
   MSW_HIP(hipStreamSynchronize(h->stream));
+}
+
+void set_dense_impl(msw_core *h, const double *Lm, size_t G, size_t E, size_t ld) {
+  if (!Lm) throw Fail("msw_core_set_dense_logl: null matrix");
+  if (G == 0 || E == 0) throw Fail("msw_core_set_dense_logl: empty likelihood");
+  if (ld < E) throw Fail("msw_core_set_dense_logl: ld < n_ecs");
+  if (E >= 0xffffffffull) throw Fail("msw_core_set_dense_logl: n_ecs exceeds 32 bits");
+  reset_likelihood(h);
+  // rows = groups, staged as they come
+  DevBuf<double> stage;
+  stage.alloc(G * E);
+  MSW_HIP(hipMemcpy2DAsync(stage.p, E * sizeof(double), Lm, ld * sizeof(double), E * sizeof(double), G,
+                           hipMemcpyHostToDevice, h->stream));
+  dense_from_stage(h, Lm, ld, stage.p, G, E);
 }
 
 // gamma (or the likelihood itself) of the ECs [e0, e1), rows = groups, columns in the caller's EC order:

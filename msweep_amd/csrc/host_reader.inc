@@ -123,13 +123,21 @@ struct DevText {
 };
 // n bytes -- of the open file fd, or of host memory `mem` when that is not null -- to dev through the stager, on its copy
 // stream; last: the last of them
-void stager_ready(ReaderCtx &cx) {
+// bytes: when given, no more threads (pinned sub-buffers: ~0.4 ms per MB to pin) than that many bytes have blocks -- the
+// likelihood-file reader's choice, whose small files would otherwise pay for 64 MB of staging; the Themisto reader, whose
+// strands are sent while the previous one's kernels run, keeps the stager at its full size
+void stager_ready(ReaderCtx &cx, uint64_t bytes = ~0ull) {
   // (reader threads: beyond ~8 the page-cache copies of these hosts stop scaling and only contend; MSWEEP_READER_THREADS
   // decides when set)
-  const size_t T0 = getenv("MSWEEP_READER_THREADS") ? reader_threads() : std::min<size_t>(reader_threads(), 8);
+  size_t T0 = getenv("MSWEEP_READER_THREADS") ? reader_threads() : std::min<size_t>(reader_threads(), 8);
+  if (bytes != ~0ull) {
+    const uint64_t B = cx.stage->block_bytes();
+    T0 = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(T0, (bytes + B - 1) / B));
+  }
   cx.stage->ready(T0);
 }
-void stage_to_device(int fd, const char *path, const char *mem, uint64_t n, unsigned char *dev, ReaderCtx &cx, unsigned char &last_out) {
+void stage_to_device(int fd, const char *path, const char *mem, uint64_t n, unsigned char *dev, ReaderCtx &cx, unsigned char &last_out,
+                     const char *noun = "pseudoalignment file") {
   const size_t B = cx.stage->block;
   const size_t T = std::max<size_t>(1, std::min<size_t>(cx.stage->threads, (size_t)((n + B - 1) / B)));
   hipStream_t cs = cx.stage->copy;
@@ -148,7 +156,7 @@ void stage_to_device(int fd, const char *path, const char *mem, uint64_t n, unsi
         size_t got_all = 0;
         while (got_all < len) {
           const ssize_t got = pread(fd, dst + got_all, len - got_all, (off_t)(off + got_all));
-          if (got <= 0) throw Fail(std::string("cannot read pseudoalignment file ") + path);
+          if (got <= 0) throw Fail(std::string("cannot read ") + noun + " " + path);
           got_all += (size_t)got;
         }
       } else {
@@ -162,21 +170,23 @@ void stage_to_device(int fd, const char *path, const char *mem, uint64_t n, unsi
   last_out = last;
 }
 bool upload_gzip_device(int fd, const char *path, uint64_t n, ReaderCtx &cx, DevText &t);  // host_inflate.inc
-void upload_text(const char *path, ReaderCtx &cx, DevText &t) {
+// noun: what the failure messages call the file (the likelihood-file reader is the other caller, host_likelihood_file.inc)
+// fit_stager: the staging area sized by the file (stager_ready)
+void upload_text(const char *path, ReaderCtx &cx, DevText &t, const char *noun = "pseudoalignment file", bool fit_stager = false) {
   const int fd = open(path, O_RDONLY);
-  if (fd < 0) throw Fail(std::string("cannot open pseudoalignment file ") + path);
+  if (fd < 0) throw Fail(std::string("cannot open ") + noun + " " + path);
   struct FdGuard {
     int fd;
     ~FdGuard() { close(fd); }
   } guard{fd};
   struct stat sb;
-  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) throw Fail(std::string("cannot open pseudoalignment file ") + path);
+  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) throw Fail(std::string("cannot open ") + noun + " " + path);
   unsigned char magic[6] = {0, 0, 0, 0, 0, 0};
   const ssize_t got_magic = pread(fd, magic, std::min<size_t>((size_t)sb.st_size, 6), 0);
   (void)got_magic;
   const bool plain = !(magic[0] == 0x1f && magic[1] == 0x8b) && !(magic[0] == 'B' && magic[1] == 'Z' && magic[2] == 'h') &&
                      !(magic[0] == 0xFD && magic[1] == '7' && magic[2] == 'z' && magic[3] == 'X' && magic[4] == 'Z');
-  stager_ready(cx);
+  stager_ready(cx, fit_stager ? (uint64_t)sb.st_size : ~0ull);
   // a gzip file goes to the device compressed and is inflated there (host_inflate.inc); where that result cannot be
   // vouched for, the host path below stands
   if (magic[0] == 0x1f && magic[1] == 0x8b && cx.inf && upload_gzip_device(fd, path, (uint64_t)sb.st_size, cx, t)) return;
@@ -194,7 +204,7 @@ void upload_text(const char *path, ReaderCtx &cx, DevText &t) {
   t.txt.alloc(padded);
   MSW_HIP(hipMemsetAsync(t.txt.p + n, '\n', padded - n, cs));
   t.last = '\n';
-  stage_to_device(fd, path, plain ? nullptr : ft.data, n, t.txt.p, cx, t.last);
+  stage_to_device(fd, path, plain ? nullptr : ft.data, n, t.txt.p, cx, t.last, noun);
   MSW_HIP(hipEventRecord(t.done, cs));
 }
 

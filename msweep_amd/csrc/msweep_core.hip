@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cerrno>
 #include <cmath>
 #include <chrono>
 #include <cstring>
@@ -42,6 +43,7 @@
 #include "deflate_kernels.hpp"
 #include "inflate_kernels.hpp"
 #include "inflate_member_kernels.hpp"
+#include "likelihood_text_kernels.hpp"
 
 using namespace msw;
 
@@ -278,6 +280,7 @@ struct msw_core {
   TextState text;
   GzState gz;
   InflateState inf;
+  std::vector<uint64_t> lik_counts;  // first column of the last served likelihood file (host_likelihood_file.inc)
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
   // ---- bootstrap -------------------------------------------------------------------------
@@ -1072,6 +1075,7 @@ struct StageTimer {
 #include "host_reader.inc"
 #include "host_inflate.inc"
 #include "host_inflate_members.inc"
+#include "host_likelihood_file.inc"
 #include "host_bin.inc"
 #include "host_text.inc"
 #include "host_gzip.inc"
@@ -1136,6 +1140,21 @@ int msw_core_shape(msw_handle h, size_t *n_groups, size_t *n_ecs, size_t *nnz) {
 
 int msw_core_set_dense_logl(msw_handle h, const double *L, size_t n_groups, size_t n_ecs, size_t ld) {
   return guarded(h, [&] { set_dense_impl(h, L, n_groups, n_ecs, ld); });
+}
+
+int msw_core_set_dense_logl_file(msw_handle h, const char *path, size_t n_groups, msw_likfile_info *info) {
+  return guarded(h, [&] {
+    if (!path) throw Fail("msw_core_set_dense_logl_file: null path");
+    set_dense_file_impl(h, path, nullptr, 0, n_groups, info);
+  });
+}
+
+int msw_core_set_dense_logl_text(msw_handle h, const char *text, size_t n, size_t n_groups, msw_likfile_info *info) {
+  return guarded(h, [&] { set_dense_file_impl(h, nullptr, text, n, n_groups, info); });
+}
+
+int msw_core_likfile_counts(msw_handle h, uint64_t *counts_out, size_t n_ecs) {
+  return guarded(h, [&] { likfile_counts_impl(h, counts_out, n_ecs); });
 }
 
 int msw_core_set_csr(msw_handle h, const uint64_t *rowptr, const uint32_t *grp, const uint32_t *cnt,

@@ -552,12 +552,16 @@ struct TextStager {
   void *pinned = nullptr;          // 2 * threads * block bytes
   std::vector<hipEvent_t> ev;      // [2 * threads]: the copy that last read a sub-buffer
   hipStream_t copy = nullptr;      // the text travels on a stream of its own: the next strand's under this strand's kernels
-  void ready(size_t T) {
+  size_t block_bytes() {
     if (!block) {
       const char *e = getenv("MSWEEP_READER_BLOCK_MB");
       const long mb = e ? atol(e) : 0;
       block = (size_t)(mb >= 1 && mb <= 256 ? mb : 4) << 20;  // (1-2 MB: the fixed cost per copy shows; 4-8 MB alike)
     }
+    return block;
+  }
+  void ready(size_t T) {
+    (void)block_bytes();
     if (T > threads) {
       release();
       MSW_HIP(hipHostMalloc(&pinned, 2 * T * block, hipHostMallocDefault));

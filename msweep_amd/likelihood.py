@@ -118,3 +118,35 @@ def from_dense(core: Core, logl, log_counts):
         raise MswError("from_dense: expected a G x E matrix")
     core.set_dense_logl(logl)
     return Likelihood(core, log_counts, np.ones(logl.shape[0], bool), logl.shape[0], logl.shape[1])
+
+
+def read_likelihood_file(path, n_groups):
+    """--read-likelihood on the host (include/Likelihood.hpp:224-253): (counts uint64 [E], matrix G x E).  A file that
+    starts with the gzip magic is inflated (gzip.open reads every member)."""
+    import gzip
+    with open(path, "rb") as probe:
+        gz = probe.read(2) == b"\x1f\x8b"
+    counts, cols = [], []
+    with (gzip.open(path, "rt") if gz else open(path)) as f:
+        for line in f:
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) != n_groups + 1:
+                raise RuntimeError("Could not read from the likelihoods file.")
+            counts.append(int(parts[0]))
+            cols.append([float(x) for x in parts[1:]])
+    return np.array(counts, np.uint64), np.ascontiguousarray(np.array(cols).T)
+
+
+def from_likelihood_file(core: Core, path, n_groups):
+    """--read-likelihood: the file parsed on the device where the device serves it (Core.set_dense_logl_file: the strict
+    grammar of include/msweep_core.h), by read_likelihood_file + from_dense otherwise -- the same resident likelihood either
+    way.  The Likelihood carries the file's first column as `ec_counts` (uint64) and msw_likfile_info as `file_info`."""
+    info, counts = core.set_dense_logl_file(path, n_groups)
+    if info["served"]:
+        lik = Likelihood(core, np.log(counts.astype(np.float64)), np.ones(n_groups, bool), n_groups, len(counts))
+    else:
+        counts, L = read_likelihood_file(path, n_groups)
+        lik = from_dense(core, L, np.log(counts.astype(np.float64)))
+    lik.ec_counts = counts
+    lik.file_info = info
+    return lik
