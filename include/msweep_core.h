@@ -402,7 +402,10 @@ void msw_alignment_destroy(msw_alignment_t a);
  * msw_alignment_view / _export copy them out on first use.  Same outcome as msw_alignment_read, array for array.
  * Text the host parser would not take silently (anything but digits, blanks and line ends, ids beyond 32 bits,
  * target ids out of range) is handed to msw_alignment_read, whose result or error message stands
- * (msw_alignment_last_error / msw_last_error). */
+ * (msw_alignment_last_error / msw_last_error).
+ * The alignment outlives every build from it: msw_core_build_likelihood_aln and msw_core_bin_reads_aln read its arrays
+ * and never modify them, so one read serves every grouping column of the -i file (the contract is stated at
+ * msw_core_build_likelihood_aln).  It is freed by msw_alignment_destroy only. */
 int msw_alignment_read_device(msw_handle h, const char *const *paths, size_t n_paths, size_t n_targets, int merge_mode,
                               msw_alignment_t *out);
 /* gzip input of msw_alignment_read_device is inflated ON THE DEVICE (msweep_amd/csrc/host_inflate.inc): the compressed
@@ -499,7 +502,19 @@ int msw_alignment_on_device(msw_alignment_t a);
  * before it is handed out again: 0.2 s at 10 M reads).  msw_core_trim gives them back; msw_core_destroy does too. */
 int msw_core_trim(msw_handle h);
 /* msw_core_build_likelihood on an alignment handle: arrays resident on h's device are read where they lie (no copy
- * through the host); any other handle goes through its host arrays.  ec_counts = the classes' read counts. */
+ * through the host); any other handle goes through its host arrays.  ec_counts = the classes' read counts.
+ * The contract of repeated builds (the grouping loop of src/mSWEEP.cpp:282: one read, one build per column of -i):
+ *   - an alignment may be built from any number of times, with any target-to-group map over the same n_targets (another
+ *     n_groups, other sizes, another --min-hits mask, in any order);
+ *   - each build REPLACES the resident likelihood and everything derived from it: the solver state (no solution, nothing
+ *     prepared), the slot tables and the record encoding, the guard lists, the trace, gamma and the EC permutation
+ *     behind its blocks.  Two things are kept because they do not depend on the likelihood: the dynamic-LDS limit
+ *     granted per sweep instantiation (only ever raised; each launch passes the size its own layout needs) and the
+ *     bootstrap's cumulative table (made from the read counts alone; reused while they are the same);
+ *   - the alignment's arrays are not modified: a build after K others reads what the first one read;
+ *   - msw_core_bin_reads_aln, msw_core_gamma*, msw_core_trace and msw_core_text_block* refer to the LATEST build and its
+ *     latest solve (a call that needs a solve fails until that build has been solved).
+ * A build on a used handle gives, bit for bit, what the same build gives on a fresh one (tests/test_gpu_groupings.py). */
 int msw_core_build_likelihood_aln(msw_handle h, msw_alignment_t a, const uint32_t *target_group, size_t n_targets,
                                   const uint64_t *group_sizes, size_t n_groups, double q, double e,
                                   double zero_inflation, size_t min_hits, size_t *n_groups_out, uint8_t *mask_out,

@@ -5,7 +5,9 @@ holds the driver's side).  The matrix outputs -- --write-probs / --print-probs, 
 --write-likelihood-bitseq -- are formatted on the device (Core.text_block): only their bytes come to the host.
 --compress z (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62) writes them and the bins as `<name>.gz`, the
 gzip stream compressed on the device as well (Core.gzip_begin / text_block_gzip / gzip_append / gzip_end); bz2, lzma
-and zstd are refused, and --compression-level 1 ... 9 all run the core's one parse (0 stores)."""
+and zstd are refused, and --compression-level 1 ... 9 all run the core's one parse (0 stores).
+Every tab-separated column of the -i file is a grouping of its own: the estimation runs once per column
+(src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several."""
 import argparse
 import math
 import os
@@ -16,7 +18,7 @@ import numpy as np
 from . import binning, parallel
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
 from .likelihood import from_device_alignment, from_likelihood_file, read_likelihood_file  # noqa: F401 (read_likelihood_file: the host parser, under its name here)
-from .reference import read_reference
+from .reference import output_path, read_references
 from .sample import BootstrapSample, PlainSample
 
 
@@ -287,21 +289,43 @@ def main(argv=None):
         # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
         sys.stderr.write("Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n")
         return 1
+    def read_indicators():
+        # every tab-separated column of -i is a grouping of its own (include/Reference.hpp:67-94); the estimation runs
+        # once per column (src/mSWEEP.cpp:282), here from ONE resident alignment
+        with open(a.indicators) as f:
+            gs = read_references(f)
+        if a.verbose and len(gs) > 1:
+            sys.stderr.write(f"  read {len(gs)} groupings\n")      # src/mSWEEP.cpp:265-267
+        return gs
+    groupings = None
+    if a.read_likelihood:
+        # more than one grouping is refused in the reference's words (src/mSWEEP.cpp:360-362), before the GPU is touched:
+        # with this flag the indicators are read first
+        try:
+            groupings = read_indicators()
+        except (RuntimeError, OSError) as ex:
+            sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
+            return 1
+        if len(groupings) > 1:
+            sys.stderr.write("Reading the likelihoods failed:\n  Using more than one grouping with --read-likelihood is not yet "
+                             "implemented.\nexiting\n")
+            return 1
     try:
         core = Core(a.device)
     except MswError as ex:
         sys.stderr.write(f"Initialising the GPU failed:\n  {ex}\nexiting\n")
         return 1
     try:
-        with open(a.indicators) as f:
-            grouping = read_reference(f)
+        if groupings is None:
+            groupings = read_indicators()
         if not a.read_likelihood:
             files = a.themisto.split(",") if a.themisto else [x for x in (a.themisto_1, a.themisto_2) if x]
             if not files:
                 raise RuntimeError("no pseudoalignment files given")
             # the reader on the device (msw_alignment_read_device): text -> equivalence classes in HBM, consumed there
             # by the likelihood build; the reference's messages for text it does not take
-            aln = core.read_alignment(files, len(grouping.group_indicators), a.themisto_mode)
+            # -- once, in front of the grouping loop: the line count of -i is the same for every column
+            aln = core.read_alignment(files, len(groupings[0].group_indicators), a.themisto_mode)
             if a.verbose:
                 # gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
                 for path, info in zip(files, core.last_inflate()):
@@ -325,6 +349,27 @@ def main(argv=None):
     try:
         # ordering the cells for the LDS banks pays from about the 1 000th iteration on: bootstrap runs (msw_core_set_pack_schedule)
         core.set_pack_schedule(a.iters >= 5)
+    except MswError as ex:
+        sys.stderr.write(f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
+        return 1
+    # the grouping loop (src/mSWEEP.cpp:282): build, outputs, solve, bins, bootstrap per column on the one handle -- every
+    # build replaces the resident likelihood and all that was derived from the one before (include/msweep_core.h).  A
+    # grouping that fails ends the run; the files of the groupings before it stay.
+    for index, grouping in enumerate(groupings):
+        rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
+        if rc:
+            return rc
+    core.close()
+    return 0
+
+
+def run_grouping(a, core, aln, grouping, index, K, algo, prec):
+    """Everything main() does per grouping column: the body of the loop at src/mSWEEP.cpp:282-563.  Returns the exit
+    status (0: go on with the next grouping)."""
+    def path(name):      # <prefix>_<name>, <prefix>_<index>_<name> when -i has several columns
+        return output_path(a.prefix, index, K, name)
+    note = f"grouping {index}: " if K > 1 else ""     # --verbose: in front of the notes of a grouping
+    try:
         if a.read_likelihood:
             # --read-likelihood (include/Likelihood.hpp:224-253): "count \t L(0,j) ... L(G-1,j)" per EC
             # -- parsed on the device where it serves the file (plain, gzip or BGZF), by read_likelihood_file otherwise
@@ -332,7 +377,7 @@ def main(argv=None):
             ec_counts, info = lik.ec_counts, lik.file_info
             if a.verbose:
                 how = f"the device ({info['n_host_cells']} cells on the host)" if info["served"] else f"the host ({info['reason_text']})"
-                sys.stderr.write(f"note: {a.read_likelihood}: likelihood file parsed on {how}\n")
+                sys.stderr.write(f"note: {note}{a.read_likelihood}: likelihood file parsed on {how}\n")
             n_reads = total_reads = int(ec_counts.sum())
         else:
             if aln.n_ecs == 0:
@@ -348,18 +393,17 @@ def main(argv=None):
         if a.write_likelihood_bitseq:
             # both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376); <prefix>_bitseq_likelihoods.tsv
             # (src/OutfileDesignator.cpp:67-74)
-            with _open_out(core, f"{a.prefix}_bitseq_likelihoods.tsv" if a.prefix else "bitseq_likelihoods.tsv", a) as f:
+            with _open_out(core, path("bitseq_likelihoods.tsv"), a) as f:
                 write_likelihood_bitseq(f, ec_counts, lik)
         elif a.write_likelihood:
             # --write-likelihood (include/Likelihood.hpp:255-273), default ostream precision; the file is
             # <prefix>_likelihoods.tsv (src/OutfileDesignator.cpp:67-74; the flag's help text says .txt)
-            with _open_out(core, f"{a.prefix}_likelihoods.tsv" if a.prefix else "likelihoods.tsv", a) as f:
+            with _open_out(core, path("likelihoods.tsv"), a) as f:
                 write_likelihood_file(f, ec_counts, lik)
     except (MswError, RuntimeError, OSError) as ex:
         sys.stderr.write(f"Writing the likelihood to file failed:\n  {ex}\nexiting\n")
         return 1
     if a.no_fit_model:
-        core.close()
         return 0
     G = lik.n_groups
     prior = np.ones(G)
@@ -376,7 +420,7 @@ def main(argv=None):
         if a.verbose:
             t = core.trace(min(res["iters"], 4096))
             for k in range(0, t["n"], 5):
-                sys.stderr.write(f"  iter: {k}, bound: {t['bound'][k]:g}, |g|: {t['newnorm'][k]:g}\n")
+                sys.stderr.write(f"  {note}iter: {k}, bound: {t['bound'][k]:g}, |g|: {t['newnorm'][k]:g}\n")
         sample.store_abundances(res["theta"])
     except MswError as ex:
         sys.stderr.write(f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
@@ -409,12 +453,12 @@ def main(argv=None):
     zero = [n for n, m in zip(names, mask) if not m]
     if a.write_probs or a.print_probs:
         # Sample::write_probs (src/Sample.cpp:63-85): header ec_id + group names, one row per EC of exp(gamma)
-        for dst in ([_open_out(core, f"{a.prefix}_probs.tsv", a, "w")] if a.write_probs and a.prefix else []) + \
+        for dst in ([_open_out(core, path("probs.tsv"), a, "w")] if a.write_probs and a.prefix else []) + \
                    ([sys.stdout] if a.print_probs or (a.write_probs and not a.prefix) else []):
             write_probs(dst, est, zero if a.min_hits > 0 else [], core)
             if dst is not sys.stdout:
                 dst.close()
-    out = open(f"{a.prefix}_abundances.txt", "w") if a.prefix else sys.stdout
+    out = open(path("abundances.txt"), "w") if a.prefix else sys.stdout
     if a.run_rate:
         # experimental RATE / KLD (src/Sample.cpp:99-152, table written at src/mSWEEP.cpp:529-545)
         kld, rate = dirichlet_kld_rate(np.asarray(sample.get_abundances()) * total)
@@ -431,7 +475,8 @@ def main(argv=None):
         sample.write_abundances(est, out)
     if a.prefix:
         out.close()
-    core.close()
+    else:
+        out.flush()
     return 0
 
 

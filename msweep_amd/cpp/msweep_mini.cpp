@@ -13,6 +13,9 @@
 // --compress z / --compression-level (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62: the matrix outputs and the
 // bins as `<name>.gz`, the gzip stream compressed on the device, msw_core_gzip_*; bz2, lzma and zstd are refused).  Same flags and messages as the reference for what it covers; held byte-for-byte against
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
+// Every tab-separated column of the -i file is a grouping of its own and the whole estimation runs once per column
+// (src/mSWEEP.cpp:282) -- from ONE read of the pseudoalignment, whose classes stay in device memory: run_grouping() is the
+// body of that loop, out_path() names its files (`<prefix>_<i>_...` when there are several; tests/test_gpu_groupings.py).
 //
 //   g++ -std=c++17 -O2 -o msweep_mini msweep_mini.cpp -L.. -lmsweep_core -Wl,-rpath,..
 #include <algorithm>
@@ -123,32 +126,56 @@ Args parse(int argc, char **argv) {
 }
 
 // ConstructAdaptiveReference / AdaptiveGrouping::add_sequence (src/Reference.cpp:31-56,
-// include/Grouping.hpp:75-80): one line per reference sequence, first tab-separated column = group
-// name, group ids in order of first appearance
+// include/Grouping.hpp:75-80, include/Reference.hpp:67-94): one line per reference sequence, one grouping per
+// tab-separated column, group ids in order of first appearance.  A line is split as repeated std::getline(..., '\t')
+// splits it (Reference.hpp:74): an empty field between two tabs is a group named "", a trailing tab adds no field; an
+// empty line stays one empty field (the group "" it has always been in a single-column file).  A line with another
+// number of fields than the first is refused (the reference would end up with columns of different lengths).
 struct Grouping {
   std::vector<std::string> names;
   std::vector<uint64_t> sizes;
   std::vector<uint32_t> indicators;
 };
-Grouping read_grouping(const std::string &path) {
+std::vector<Grouping> read_groupings(const std::string &path) {
   std::ifstream in(path);
   if (!in) throw std::runtime_error("cannot open " + path);
-  Grouping g;
-  std::unordered_map<std::string, uint32_t> ids;
+  std::vector<Grouping> gs;
+  std::vector<std::unordered_map<std::string, uint32_t>> ids;
   std::string line;
+  size_t n_lines = 0;
   while (std::getline(in, line)) {
-    const std::string name = line.substr(0, line.find('\t'));
-    auto it = ids.find(name);
-    if (it == ids.end()) {
-      it = ids.emplace(name, (uint32_t)g.names.size()).first;
-      g.names.push_back(name);
-      g.sizes.push_back(0);
+    ++n_lines;
+    std::vector<std::string> fields = split(line, '\t');
+    if (fields.empty()) fields.emplace_back();
+    if (n_lines == 1) {
+      gs.resize(fields.size());
+      ids.resize(fields.size());
     }
-    ++g.sizes[it->second];
-    g.indicators.push_back(it->second);
+    if (fields.size() != gs.size())
+      throw std::runtime_error("The grouping has " + std::to_string(fields.size()) + " columns on line " + std::to_string(n_lines) +
+                               ", " + std::to_string(gs.size()) + " on line 1");
+    for (size_t c = 0; c < gs.size(); ++c) {
+      Grouping &g = gs[c];
+      auto it = ids[c].find(fields[c]);
+      if (it == ids[c].end()) {
+        it = ids[c].emplace(fields[c], (uint32_t)g.names.size()).first;
+        g.names.push_back(fields[c]);
+        g.sizes.push_back(0);
+      }
+      ++g.sizes[it->second];
+      g.indicators.push_back(it->second);
+    }
   }
-  if (g.indicators.empty()) throw std::runtime_error("The grouping contains 0 reference sequences");
-  return g;
+  if (gs.empty()) throw std::runtime_error("The grouping contains 0 reference sequences");
+  return gs;
+}
+
+// The file of an output of grouping `index` of K (src/OutfileDesignator.cpp:64-74,116-123): `<prefix>_<name>` for a
+// single grouping, `<prefix>_<index>_<name>` when -i has several columns; without a prefix the bare name (the
+// likelihood files: everything else goes to stdout then).  msweep_amd/reference.py output_path is the same function.
+std::string out_path(const std::string &prefix, size_t index, size_t K, const std::string &name) {
+  if (prefix.empty()) return name;
+  return K > 1 ? prefix + "_" + std::to_string(index) + "_" + name : prefix + "_" + name;
 }
 
 void check(msw_handle h, int rc) {
@@ -554,6 +581,200 @@ void dirichlet_kld_rate(const std::vector<double> &alphas, std::vector<double> &
   }
 }
 
+// what the groupings of one run share: the handle and the alignment read once in front of the loop
+struct Run {
+  msw_handle h = nullptr;
+  msw_alignment_t aln = nullptr;
+  size_t n_ecs = 0, n_reads = 0, n_groupings = 1;
+  std::vector<uint64_t> ec_counts;
+  int algo = MSW_ALGO_RCG, prec = MSW_PREC_DOUBLE;
+};
+
+// Everything main() does per grouping column -- the body of the loop at src/mSWEEP.cpp:282-563: the device build with
+// this column's indicators (it replaces the resident likelihood and all that was derived from the one before,
+// include/msweep_core.h), the likelihood outputs, the solve, the bins, the bootstrap, the probabilities and the
+// abundances.  Returns the exit status (0: go on with the next grouping).
+int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t index) {
+  msw_handle h = r.h;
+  const size_t K = r.n_groupings;
+  const std::string note = K > 1 ? "grouping " + std::to_string(index) + ": " : std::string();  // --verbose
+  const size_t G = grouping.names.size();
+  size_t n_ecs = r.n_ecs, n_reads = r.n_reads, n_kept = 0;
+  std::vector<uint64_t> file_counts;  // --read-likelihood: the first column of the file
+  const std::vector<uint64_t> &ec_counts = a.read_likelihood.empty() ? r.ec_counts : file_counts;
+  std::vector<uint8_t> mask(G, 1);
+  std::vector<double> logc_file;  // --read-likelihood: the log counts of the file (the build leaves its own on the device)
+  try {
+    if (!a.read_likelihood.empty()) {
+      // --read-likelihood (include/Likelihood.hpp:224-253): the dense matrix of a file through the dense boundary
+      // -- parsed on the device where it serves the file (plain, gzip or BGZF), by read_likelihood_file otherwise
+      msw_likfile_info lf;
+      check(h, msw_core_set_dense_logl_file(h, a.read_likelihood.c_str(), G, &lf));
+      if (a.verbose) {
+        static const char *const why[] = {"none", "forced", "open / read", "bad byte", "bad token", "column count", "empty",
+                                          "too many host cells", "range error", "memory", "too many lines"};
+        std::cerr << "note: " << note << a.read_likelihood << ": likelihood file parsed on ";
+        if (lf.served) std::cerr << "the device (" << lf.n_host_cells << " cells on the host)\n";
+        else std::cerr << "the host (" << why[lf.reason >= 0 && lf.reason < 11 ? lf.reason : 0] << ")\n";
+      }
+      if (lf.served) {
+        n_ecs = (size_t)lf.n_ecs;
+        file_counts.resize(n_ecs);
+        check(h, msw_core_likfile_counts(h, file_counts.data(), n_ecs));
+      } else {
+        std::vector<double> L;
+        read_likelihood_file(h, a.read_likelihood, G, file_counts, L);
+        n_ecs = file_counts.size();
+        if (n_ecs == 0) throw std::runtime_error("Could not read from the likelihoods file.");
+        check(h, msw_core_set_dense_logl(h, L.data(), G, n_ecs, n_ecs));
+      }
+      n_kept = G;
+      for (uint64_t c : file_counts) {
+        logc_file.push_back(std::log((double)c));
+        n_reads += c;   // (no alignment: the reads are those the file counts, as the Python mirror reports them)
+      }
+    } else {
+      if (n_ecs == 0) throw std::runtime_error("no read aligned against the reference");
+      check(h, msw_core_build_likelihood_aln(h, r.aln, grouping.indicators.data(), grouping.indicators.size(),
+                                             grouping.sizes.data(), G, a.q, a.e, a.zero_inflation, a.min_hits, &n_kept,
+                                             mask.data(), nullptr));
+      // (the pseudoalignment stays: the next grouping is built from it, and --bin-reads reads its classes)
+    }
+  } catch (const std::exception &ex) {
+    std::cerr << "Building the log-likelihood array failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  try {
+    // written here if requested (src/mSWEEP.cpp:373-380: a failure has a message of its own)
+    if (a.write_likelihood_bitseq) {
+      // both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376)
+      Out lf(h, out_path(a.prefix, index, K, "bitseq_likelihoods.tsv"), a.compress == "z", a.compression_level);
+      write_likelihood_bitseq(lf, h, ec_counts, n_kept, n_ecs);
+    } else if (a.write_likelihood) {
+      // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
+      Out lf(h, out_path(a.prefix, index, K, "likelihoods.tsv"), a.compress == "z", a.compression_level);
+      write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
+    }
+  } catch (const std::exception &ex) {
+    std::cerr << "Writing the likelihood to file failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  if (a.no_fit_model) return 0;  // src/mSWEEP.cpp:385-386
+  std::vector<double> prior(n_kept, 1.0);
+  if (!a.alphas.empty()) {
+    // checked against THIS grouping's group count when it is reached (src/mSWEEP.cpp:392-396)
+    const auto parts = split(a.alphas, ',');
+    if (parts.size() != n_kept) {
+      std::cerr << "Error: --alphas must have the same number of values as there are groups.";
+      return 1;
+    }
+    for (size_t i = 0; i < n_kept; ++i) prior[i] = std::stod(parts[i]);
+  }
+  uint64_t total = 0;
+  for (uint64_t c : ec_counts) total += c;
+  std::vector<std::string> est_names, zero_names;
+  for (size_t g = 0; g < G; ++g) (mask[g] ? est_names : zero_names).push_back(grouping.names[g]);
+  std::vector<std::vector<double>> results;  // [0] = estimate without resampling (include/Sample.hpp:157)
+  try {
+    std::vector<double> theta(n_kept);
+    size_t it = 0;
+    double bound = 0.0;
+    // logc = NULL: the log counts stay where the build left them, on the device
+    check(h, msw_core_solve(h, logc_file.empty() ? nullptr : logc_file.data(), prior.data(), a.tol, a.max_iters, r.algo, r.prec,
+                            theta.data(), &it, &bound));
+    if (a.verbose) {
+      const size_t n = std::min<size_t>(it, 4096);
+      std::vector<double> b(n), nn(n);
+      size_t got = 0;
+      check(h, msw_core_trace(h, n, b.data(), nn.data(), nullptr, nullptr, nullptr, &got));
+      char buf[128];
+      for (size_t k = 0; k < got; k += 5) {
+        snprintf(buf, sizeof buf, "iter: %zu, bound: %g, |g|: %g\n", k, b[k], nn[k]);
+        std::cerr << "  " << note << buf;
+      }
+    }
+    results.push_back(theta);
+    if (a.bin_reads) {
+      // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
+      if (bin_reads(a, h, r.aln, est_names, theta) != 0) return 1;
+    }
+    if (a.iters > 0) {
+      // every grouping's bootstrap starts the stream from the same seed (the reference constructs the sample inside its
+      // loop); the random-seed sentinel draws anew per grouping
+      int32_t seed;
+      if (a.seed == 26012023) {  // the reference's "random seed" sentinel (src/BootstrapSample.cpp:48-50)
+        seed = (int32_t)(std::random_device{}() & 0x7fffffffu);
+      } else {
+        seed = (int32_t)(uint32_t)a.seed;  // size_t -> int32 narrowing (include/Sample.hpp:169)
+      }
+      // ConstructSample (src/Sample.cpp:30-50): --bootstrap-count is the number of draws with --bin-reads; the quirk
+      // without it passes the number of ITERATIONS as the count
+      const size_t draws = a.bootstrap_count > 0 ? (a.bin_reads ? a.bootstrap_count : a.iters) : (size_t)total;
+      std::vector<uint32_t> w(ec_counts.begin(), ec_counts.end());
+      std::vector<double> thetas(a.iters * n_kept);
+      check(h, msw_core_bootstrap(h, w.data(), seed, draws, 0, a.iters, prior.data(), a.tol, a.max_iters, r.algo, r.prec,
+                                  thetas.data(), nullptr));
+      for (size_t b = 0; b < a.iters; ++b)
+        results.emplace_back(thetas.begin() + b * n_kept, thetas.begin() + (b + 1) * n_kept);
+    }
+    // --write-probs / --print-probs: the probabilities of the un-resampled estimate (the replicates ran on solver
+    // states of their own: the handle still holds it -- the reference writes them before its replicate loop,
+    // src/mSWEEP.cpp:471-493)
+    if (a.write_probs || a.print_probs) {
+      const std::vector<std::string> none;
+      const std::vector<std::string> &zn = a.min_hits > 0 ? zero_names : none;
+      if (a.write_probs && !a.prefix.empty()) {
+        Out pf(h, out_path(a.prefix, index, K, "probs.tsv"), a.compress == "z", a.compression_level);
+        write_probs(pf, h, est_names, zn, n_kept, n_ecs);
+      }
+      if (a.print_probs || (a.write_probs && a.prefix.empty())) {
+        Out so(h, std::cout);
+        write_probs(so, h, est_names, zn, n_kept, n_ecs);
+      }
+    }
+  } catch (const std::exception &ex) {
+    std::cerr << "Estimating relative abundances failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+
+  // ---- abundances (default ostream formatting = 6 significant digits, as the reference) ----------
+  std::ofstream file;
+  if (!a.prefix.empty()) file.open(out_path(a.prefix, index, K, "abundances.txt"));
+  std::ostream &of = a.prefix.empty() ? std::cout : file;
+  of << "#mSWEEP_version:\t" << kVersion << '\n' << "#num_reads:\t" << n_reads << '\n' << "#num_aligned:\t" << total << '\n';
+  if (a.run_rate) {
+    // experimental RATE / KLD (src/Sample.cpp:99-152; the table: src/mSWEEP.cpp:529-545)
+    std::vector<double> alphas(n_kept), kld, rate;
+    for (size_t i = 0; i < n_kept; ++i) alphas[i] = results[0][i] * (double)total;
+    dirichlet_kld_rate(alphas, kld, rate);
+    of << "#c_id\tmean_theta\tRATE\tKLD\n";
+    for (size_t i = 0; i < n_kept; ++i)
+      of << est_names[i] << '\t' << g6(results[0][i]) << '\t' << g6(rate[i]) << '\t' << g6(kld[i]) << '\n';
+    for (auto &n : zero_names) of << n << "\t0\t0\t0\n";
+    of.flush();
+    return 0;
+  }
+  if (a.iters > 0) of << "#bootstrap_iters:\t" << a.iters << '\n' << "#c_id\tmean_theta\tbootstrap_mean_thetas\n";
+  else of << "#c_id\tmean_theta\n";
+  size_t row = 0;
+  for (size_t g = 0; g < G; ++g) {  // estimated groups (all of them unless --min-hits pruned some)
+    if (!mask[g]) continue;
+    of << grouping.names[g];
+    for (auto &res : results) of << '\t' << res[row];
+    of << '\n';
+    ++row;
+  }
+  if (a.min_hits > 0)
+    for (size_t g = 0; g < G; ++g) {
+      if (mask[g]) continue;
+      of << grouping.names[g];
+      for (size_t k = 0; k < results.size(); ++k) of << "\t0";
+      of << '\n';
+    }
+  of.flush();
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -581,28 +802,47 @@ int main(int argc, char **argv) {
     std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
     return 1;
   }
-  Grouping grouping;
-  std::vector<uint64_t> ec_counts;
+  // every tab-separated column of -i is a grouping of its own; the estimation runs once per column
+  // (src/mSWEEP.cpp:282), here from ONE resident alignment
+  std::vector<Grouping> groupings;
+  auto read_indicators = [&] {
+    groupings = read_groupings(a.indicators);
+    if (a.verbose && groupings.size() > 1) std::cerr << "  read " << groupings.size() << " groupings\n";  // src/mSWEEP.cpp:265-267
+  };
+  if (!a.read_likelihood.empty()) {
+    // more than one grouping is refused in the reference's words (src/mSWEEP.cpp:360-362), before the GPU is touched:
+    // with this flag the indicators are read first
+    try {
+      read_indicators();
+    } catch (const std::exception &ex) {
+      std::cerr << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
+      return 1;
+    }
+    if (groupings.size() > 1) {
+      std::cerr << "Reading the likelihoods failed:\n  Using more than one grouping with --read-likelihood is not yet implemented.\nexiting\n";
+      return 1;
+    }
+  }
+  Run r;
   // The reader runs ON THE DEVICE (msw_alignment_read_device: text -> equivalence classes in HBM) and the likelihood
-  // build consumes its arrays there (msw_core_build_likelihood_aln); only the classes' read counts come to the host.
-  msw_handle h = nullptr;
-  if (msw_core_create(a.gpu, &h) != 0) {
+  // builds consume its arrays there (msw_core_build_likelihood_aln); only the classes' read counts come to the host.
+  if (msw_core_create(a.gpu, &r.h) != 0) {
     std::cerr << "Initialising the GPU failed:\n  " << msw_last_error(nullptr) << "\nexiting\n";
     return 1;
   }
-  msw_alignment_t aln_keep = nullptr;
-  size_t n_ecs = 0, n_reads = 0, n_hits = 0, n_aligned = 0;
+  msw_handle h = r.h;
   try {
-    grouping = read_grouping(a.indicators);
+    if (groupings.empty()) read_indicators();
+    r.n_groupings = groupings.size();
     if (a.read_likelihood.empty()) {  // (--read-likelihood needs no pseudoalignments: src/mSWEEP.cpp:296-370)
       if (a.themisto.empty()) throw std::runtime_error("no pseudoalignment files given");
       if (a.mode != "intersection" && a.mode != "union")
         throw std::runtime_error("Unrecognized option `" + a.mode + "` for --themisto-mode");
       std::vector<const char *> paths;
       for (auto &p : a.themisto) paths.push_back(p.c_str());
-      msw_alignment_t aln = nullptr;
-      if (msw_alignment_read_device(h, paths.data(), paths.size(), grouping.indicators.size(),
-                                    a.mode == "union" ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION, &aln))
+      // once, in front of the grouping loop: the line count of -i is the same for every column
+      if (msw_alignment_read_device(h, paths.data(), paths.size(), groupings[0].indicators.size(),
+                                    a.mode == "union" ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION, &r.aln))
         throw std::runtime_error(msw_alignment_last_error());
       if (a.verbose) {
         // gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
@@ -618,10 +858,10 @@ int main(int argc, char **argv) {
             else std::cerr << "the host (" << why[info[i].fallback_reason >= 0 && info[i].fallback_reason < 9 ? info[i].fallback_reason : 0] << ")\n";
           }
       }
-      msw_alignment_shape(aln, &n_ecs, &n_reads, &n_hits, &n_aligned);
-      ec_counts.resize(n_ecs);
-      msw_alignment_export(aln, nullptr, nullptr, ec_counts.data(), nullptr, nullptr);
-      aln_keep = aln;
+      size_t n_hits = 0, n_aligned = 0;
+      msw_alignment_shape(r.aln, &r.n_ecs, &r.n_reads, &n_hits, &n_aligned);
+      r.ec_counts.resize(r.n_ecs);
+      msw_alignment_export(r.aln, nullptr, nullptr, r.ec_counts.data(), nullptr, nullptr);
     }
   } catch (const std::exception &ex) {
     std::cerr << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
@@ -630,194 +870,20 @@ int main(int argc, char **argv) {
   }
   if (a.algorithm == "rcgcpu" && a.verbose)  // the reference's default: the same RCG algorithm on the host; no CPU path here
     std::cerr << "note: --algorithm rcgcpu is served by the GPU RCG kernels (same algorithm as rcggpu)\n";
-  const int algo = (a.algorithm == "rcggpu" || a.algorithm == "rcgcpu") ? MSW_ALGO_RCG : MSW_ALGO_EM;  // else em (src/mSWEEP.cpp:200)
-  const int prec = a.emprecision == "float" ? MSW_PREC_FLOAT : MSW_PREC_DOUBLE;
+  r.algo = (a.algorithm == "rcggpu" || a.algorithm == "rcgcpu") ? MSW_ALGO_RCG : MSW_ALGO_EM;  // else em (src/mSWEEP.cpp:200)
+  r.prec = a.emprecision == "float" ? MSW_PREC_FLOAT : MSW_PREC_DOUBLE;
   // (--emprecision float: fp32 kernels where the layout allows, msweep_amd/csrc/em_f32_kernels.hpp)
-  const size_t G = grouping.names.size();
-  size_t n_kept = 0;
-  std::vector<uint8_t> mask(G, 1);
-  std::vector<double> logc_file;  // --read-likelihood: the log counts of the file (the build leaves its own on the device)
-  try {
-    // ordering the cells for the LDS banks pays from about the 1 000th iteration on: bootstrap runs
-    check(h, msw_core_set_pack_schedule(h, a.iters >= 5 ? 1 : 0));
-    if (!a.read_likelihood.empty()) {
-      // --read-likelihood (include/Likelihood.hpp:224-253): the dense matrix of a file through the dense boundary
-      // -- parsed on the device where it serves the file (plain, gzip or BGZF), by read_likelihood_file otherwise
-      msw_likfile_info lf;
-      check(h, msw_core_set_dense_logl_file(h, a.read_likelihood.c_str(), G, &lf));
-      if (a.verbose) {
-        static const char *const why[] = {"none", "forced", "open / read", "bad byte", "bad token", "column count", "empty",
-                                          "too many host cells", "range error", "memory", "too many lines"};
-        std::cerr << "note: " << a.read_likelihood << ": likelihood file parsed on ";
-        if (lf.served) std::cerr << "the device (" << lf.n_host_cells << " cells on the host)\n";
-        else std::cerr << "the host (" << why[lf.reason >= 0 && lf.reason < 11 ? lf.reason : 0] << ")\n";
-      }
-      if (lf.served) {
-        n_ecs = (size_t)lf.n_ecs;
-        ec_counts.resize(n_ecs);
-        check(h, msw_core_likfile_counts(h, ec_counts.data(), n_ecs));
-      } else {
-        std::vector<double> L;
-        read_likelihood_file(h, a.read_likelihood, G, ec_counts, L);
-        n_ecs = ec_counts.size();
-        if (n_ecs == 0) throw std::runtime_error("Could not read from the likelihoods file.");
-        check(h, msw_core_set_dense_logl(h, L.data(), G, n_ecs, n_ecs));
-      }
-      n_kept = G;
-      for (uint64_t c : ec_counts) {
-        logc_file.push_back(std::log((double)c));
-        n_reads += c;   // (no alignment: the reads are those the file counts, as the Python mirror reports them)
-      }
-    } else {
-      if (n_ecs == 0) throw std::runtime_error("no read aligned against the reference");
-      check(h, msw_core_build_likelihood_aln(h, aln_keep, grouping.indicators.data(), grouping.indicators.size(),
-                                             grouping.sizes.data(), G, a.q, a.e, a.zero_inflation, a.min_hits, &n_kept,
-                                             mask.data(), nullptr));
-      // (the likelihood is resident and the pseudoalignment could go -- but device memory given back is scrubbed before
-      // it is handed out again, and the solver state is allocated next: it goes at the end)
-    }
-  } catch (const std::exception &ex) {
-    std::cerr << "Building the log-likelihood array failed:\n  " << ex.what() << "\nexiting\n";
-    msw_core_destroy(h);
-    return 1;
+  int rc = 0;
+  // ordering the cells for the LDS banks pays from about the 1 000th iteration on: bootstrap runs
+  if (msw_core_set_pack_schedule(h, a.iters >= 5 ? 1 : 0) != 0) {
+    std::cerr << "Building the log-likelihood array failed:\n  " << msw_last_error(h) << "\nexiting\n";
+    rc = 1;
   }
-  try {
-    // written here if requested (src/mSWEEP.cpp:373-380: a failure has a message of its own)
-    if (a.write_likelihood_bitseq) {
-      // both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376)
-      Out lf(h, a.prefix.empty() ? std::string("bitseq_likelihoods.tsv") : a.prefix + "_bitseq_likelihoods.tsv", a.compress == "z",
-             a.compression_level);
-      write_likelihood_bitseq(lf, h, ec_counts, n_kept, n_ecs);
-    } else if (a.write_likelihood) {
-      // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
-      Out lf(h, a.prefix.empty() ? std::string("likelihoods.tsv") : a.prefix + "_likelihoods.tsv", a.compress == "z", a.compression_level);
-      write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
-    }
-  } catch (const std::exception &ex) {
-    std::cerr << "Writing the likelihood to file failed:\n  " << ex.what() << "\nexiting\n";
-    msw_core_destroy(h);
-    return 1;
-  }
-  if (a.no_fit_model) {  // src/mSWEEP.cpp:385-386
-    msw_core_destroy(h);
-    return 0;
-  }
-  std::vector<double> prior(n_kept, 1.0);
-  if (!a.alphas.empty()) {
-    const auto parts = split(a.alphas, ',');
-    if (parts.size() != n_kept) {
-      std::cerr << "Error: --alphas must have the same number of values as there are groups.";
-      msw_core_destroy(h);
-      return 1;
-    }
-    for (size_t i = 0; i < n_kept; ++i) prior[i] = std::stod(parts[i]);
-  }
-  uint64_t total = 0;
-  for (uint64_t c : ec_counts) total += c;
-  std::vector<std::string> est_names, zero_names;
-  for (size_t g = 0; g < G; ++g) (mask[g] ? est_names : zero_names).push_back(grouping.names[g]);
-  std::vector<std::vector<double>> results;  // [0] = estimate without resampling (include/Sample.hpp:157)
-  try {
-    std::vector<double> theta(n_kept);
-    size_t it = 0;
-    double bound = 0.0;
-    // logc = NULL: the log counts stay where the build left them, on the device
-    check(h, msw_core_solve(h, logc_file.empty() ? nullptr : logc_file.data(), prior.data(), a.tol, a.max_iters, algo, prec,
-                            theta.data(), &it, &bound));
-    if (a.verbose) {
-      const size_t n = std::min<size_t>(it, 4096);
-      std::vector<double> b(n), nn(n);
-      size_t got = 0;
-      check(h, msw_core_trace(h, n, b.data(), nn.data(), nullptr, nullptr, nullptr, &got));
-      char buf[128];
-      for (size_t k = 0; k < got; k += 5) {
-        snprintf(buf, sizeof buf, "  iter: %zu, bound: %g, |g|: %g\n", k, b[k], nn[k]);
-        std::cerr << buf;
-      }
-    }
-    results.push_back(theta);
-    if (a.bin_reads) {
-      // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
-      if (bin_reads(a, h, aln_keep, est_names, theta) != 0) {
-        msw_alignment_destroy(aln_keep);
-        msw_core_destroy(h);
-        return 1;
-      }
-    }
-    if (a.iters > 0) {
-      int32_t seed;
-      if (a.seed == 26012023) {  // the reference's "random seed" sentinel (src/BootstrapSample.cpp:48-50)
-        seed = (int32_t)(std::random_device{}() & 0x7fffffffu);
-      } else {
-        seed = (int32_t)(uint32_t)a.seed;  // size_t -> int32 narrowing (include/Sample.hpp:169)
-      }
-      // ConstructSample (src/Sample.cpp:30-50): --bootstrap-count is the number of draws with --bin-reads; the quirk
-      // without it passes the number of ITERATIONS as the count
-      const size_t draws = a.bootstrap_count > 0 ? (a.bin_reads ? a.bootstrap_count : a.iters) : (size_t)total;
-      std::vector<uint32_t> w(ec_counts.begin(), ec_counts.end());
-      std::vector<double> thetas(a.iters * n_kept);
-      check(h, msw_core_bootstrap(h, w.data(), seed, draws, 0, a.iters, prior.data(), a.tol, a.max_iters, algo, prec,
-                                  thetas.data(), nullptr));
-      for (size_t b = 0; b < a.iters; ++b)
-        results.emplace_back(thetas.begin() + b * n_kept, thetas.begin() + (b + 1) * n_kept);
-    }
-    // --write-probs / --print-probs: the probabilities of the un-resampled estimate (the replicates ran on solver
-    // states of their own: the handle still holds it -- the reference writes them before its replicate loop,
-    // src/mSWEEP.cpp:471-493)
-    if (a.write_probs || a.print_probs) {
-      const std::vector<std::string> none;
-      const std::vector<std::string> &zn = a.min_hits > 0 ? zero_names : none;
-      if (a.write_probs && !a.prefix.empty()) {
-        Out pf(h, a.prefix + "_probs.tsv", a.compress == "z", a.compression_level);
-        write_probs(pf, h, est_names, zn, n_kept, n_ecs);
-      }
-      if (a.print_probs || (a.write_probs && a.prefix.empty())) {
-        Out so(h, std::cout);
-        write_probs(so, h, est_names, zn, n_kept, n_ecs);
-      }
-    }
-  } catch (const std::exception &ex) {
-    std::cerr << "Estimating relative abundances failed:\n  " << ex.what() << "\nexiting\n";
-    msw_core_destroy(h);
-    return 1;
-  }
-  msw_alignment_destroy(aln_keep);
+  // the grouping loop: a grouping that fails ends the run, the files of the groupings before it stay
+  for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(a, r, groupings[i], i);
+  // (the pseudoalignment goes at the end: device memory given back is scrubbed before it is handed out again, and the
+  // solver state is allocated after the build)
+  msw_alignment_destroy(r.aln);
   msw_core_destroy(h);
-
-  // ---- abundances (default ostream formatting = 6 significant digits, as the reference) ----------
-  std::ofstream file;
-  if (!a.prefix.empty()) file.open(a.prefix + "_abundances.txt");
-  std::ostream &of = a.prefix.empty() ? std::cout : file;
-  of << "#mSWEEP_version:\t" << kVersion << '\n' << "#num_reads:\t" << n_reads << '\n' << "#num_aligned:\t" << total << '\n';
-  if (a.run_rate) {
-    // experimental RATE / KLD (src/Sample.cpp:99-152; the table: src/mSWEEP.cpp:529-545)
-    std::vector<double> alphas(n_kept), kld, rate;
-    for (size_t i = 0; i < n_kept; ++i) alphas[i] = results[0][i] * (double)total;
-    dirichlet_kld_rate(alphas, kld, rate);
-    of << "#c_id\tmean_theta\tRATE\tKLD\n";
-    for (size_t i = 0; i < n_kept; ++i)
-      of << est_names[i] << '\t' << g6(results[0][i]) << '\t' << g6(rate[i]) << '\t' << g6(kld[i]) << '\n';
-    for (auto &n : zero_names) of << n << "\t0\t0\t0\n";
-    of.flush();
-    return 0;
-  }
-  if (a.iters > 0) of << "#bootstrap_iters:\t" << a.iters << '\n' << "#c_id\tmean_theta\tbootstrap_mean_thetas\n";
-  else of << "#c_id\tmean_theta\n";
-  size_t row = 0;
-  for (size_t g = 0; g < G; ++g) {  // estimated groups (all of them unless --min-hits pruned some)
-    if (!mask[g]) continue;
-    of << grouping.names[g];
-    for (auto &r : results) of << '\t' << r[row];
-    of << '\n';
-    ++row;
-  }
-  if (a.min_hits > 0)
-    for (size_t g = 0; g < G; ++g) {
-      if (mask[g]) continue;
-      of << grouping.names[g];
-      for (size_t k = 0; k < results.size(); ++k) of << "\t0";
-      of << '\n';
-    }
-  of.flush();
-  return 0;
+  return rc;
 }

@@ -103,7 +103,10 @@ class DeviceLikelihood {
   explicit DeviceLikelihood(int device = 0) {
     if (msw_core_create(device, &h_) != 0) throw std::runtime_error(msw_last_error(nullptr));
   }
-  ~DeviceLikelihood() { msw_core_destroy(h_); }
+  ~DeviceLikelihood() {
+    release_alignment();
+    msw_core_destroy(h_);
+  }
   DeviceLikelihood(const DeviceLikelihood &) = delete;
   DeviceLikelihood &operator=(const DeviceLikelihood &) = delete;
   msw_handle handle() const { return h_; }
@@ -154,31 +157,52 @@ class DeviceLikelihood {
   // counts are.  Text the kernels do not judge goes through the host parser: the reference's messages.
   void build_from_files(const std::vector<std::string> &paths, bool union_mode, const std::vector<uint32_t> &target_group,
                         const std::vector<uint64_t> &group_sizes, double q, double e, size_t min_hits, double zero_inflation) {
+    read_files(paths, union_mode, target_group.size());
+    struct Guard {  // as before the split: the pseudoalignment does not outlive the call
+      DeviceLikelihood *d;
+      ~Guard() { d->release_alignment(); }
+    } guard{this};
+    build_from_alignment(target_group, group_sizes, q, e, min_hits, zero_inflation);
+  }
+  // The two halves of build_from_files, for the reference's grouping loop (src/mSWEEP.cpp:282): ONE read_files in front
+  // of the loop -- n_targets = the line count of -i, the same for every column -- and one build_from_alignment per
+  // grouping.  read_files keeps the alignment (device-resident) in the object and fills ec_counts(), n_reads() and
+  // n_aligned(); it is destroyed with the object, by the next read_files or by release_alignment().
+  void read_files(const std::vector<std::string> &paths, bool union_mode, size_t n_targets) {
     std::vector<const char *> c;
     for (const auto &p : paths) c.push_back(p.c_str());
-    msw_alignment_t aln = nullptr;
-    if (msw_alignment_read_device(h_, c.data(), c.size(), target_group.size(), union_mode ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION,
-                                  &aln))
+    release_alignment();
+    if (msw_alignment_read_device(h_, c.data(), c.size(), n_targets, union_mode ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION, &aln_))
       throw std::runtime_error(msw_alignment_last_error());
-    struct Guard {
-      msw_alignment_t a;
-      ~Guard() { msw_alignment_destroy(a); }
-    } guard{aln};
     size_t E = 0, hits = 0;
-    msw_alignment_shape(aln, &E, &n_reads_, &hits, &n_aligned_);
-    if (E == 0) throw std::runtime_error("no read aligned against the reference");
+    msw_alignment_shape(aln_, &E, &n_reads_, &hits, &n_aligned_);
     ec_counts_.assign(E, 0);
-    if (msw_alignment_export(aln, nullptr, nullptr, ec_counts_.data(), nullptr, nullptr))
+    if (E && msw_alignment_export(aln_, nullptr, nullptr, ec_counts_.data(), nullptr, nullptr)) {
+      release_alignment();
       throw std::runtime_error("msw_alignment_export failed");
-    const size_t G = group_sizes.size();
+    }
+  }
+  // Callable once per grouping, in any order, with any target-to-group map over the n_targets read_files was given: each
+  // call replaces the resident likelihood and everything derived from it (include/msweep_core.h); the alignment is only
+  // read.  Afterwards log_counts() / groups_considered() / n_groups() describe THIS grouping.
+  void build_from_alignment(const std::vector<uint32_t> &target_group, const std::vector<uint64_t> &group_sizes, double q,
+                            double e, size_t min_hits, double zero_inflation) {
+    if (!aln_) throw std::runtime_error("DeviceLikelihood::build_from_alignment: no alignment (read_files first)");
+    const size_t E = ec_counts_.size(), G = group_sizes.size();
+    if (E == 0) throw std::runtime_error("no read aligned against the reference");
     std::vector<uint8_t> mask(G, 0);
     logc_.assign(E, 0.0);
     size_t kept = 0;
-    check(h_, msw_core_build_likelihood_aln(h_, aln, target_group.data(), target_group.size(), group_sizes.data(), G, q, e,
+    check(h_, msw_core_build_likelihood_aln(h_, aln_, target_group.data(), target_group.size(), group_sizes.data(), G, q, e,
                                             zero_inflation, min_hits, &kept, mask.data(), logc_.data()));
     mask_.assign(mask.begin(), mask.end());
     built_ = true;
   }
+  void release_alignment() {
+    if (aln_) msw_alignment_destroy(aln_);
+    aln_ = nullptr;
+  }
+  msw_alignment_t alignment() const { return aln_; }   // the alignment read_files keeps (msw_core_bin_reads_aln)
   // LL_WOR21::from_file (include/Likelihood.hpp:224-253), the mirror of --read-likelihood: one line per class,
   // `count \t L(0,j) ... L(n_groups-1,j)`, plain, gzip or BGZF.  The device parses what it serves
   // (msw_core_set_dense_logl_file: a strict grammar); any other text is read here, cell by cell, and uploaded through
@@ -265,6 +289,7 @@ class DeviceLikelihood {
 
  private:
   msw_handle h_ = nullptr;
+  msw_alignment_t aln_ = nullptr;  // read_files
   std::vector<double> logc_;
   std::vector<uint64_t> ec_counts_;
   size_t n_reads_ = 0, n_aligned_ = 0;
