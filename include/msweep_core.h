@@ -494,6 +494,56 @@ int msw_core_set_dense_logl_file(msw_handle h, const char *path, size_t n_groups
 int msw_core_set_dense_logl_text(msw_handle h, const char *text, size_t n, size_t n_groups, msw_likfile_info *info);
 /* first column of the last served file: the read counts of its n_ecs lines */
 int msw_core_likfile_counts(msw_handle h, uint64_t *counts_out, size_t n_ecs);
+
+/* ---- --extract-reads: the binned reads themselves, from the FASTQ files (docs/pipeline.md:59-64 runs a second tool,
+ * `mGEMS extract`, for this step) ---------------------------------------------------------------------------------------
+ * A read file -- plain, gzip or BGZF: the same upload as msw_alignment_read_device, inflate included -- becomes resident
+ * on h's device with an index of its records (msweep_amd/csrc/fastq_kernels.hpp, host_fastq.inc); a selection of read ids
+ * -- a bin of msw_core_bin_reads -- is then gathered there, and its records come back as plain bytes or inside the
+ * handle's open gzip stream, where only compressed bytes cross the link.
+ * The grammar is the strict four-line one: a record is four lines, the first begins with '@', the third with '+', the
+ * second and the fourth have the same length (a '\r' in front of the '\n' counts on both), the line count is a multiple
+ * of 4; a last line without '\n' counts as a line.  Lines are counted, '@' is never searched for.  Read id i is the
+ * i-th record of the file, from 0; ids are below 2^32.  One text is resident per file, whole.
+ * msw_fastq_open    reason / bad_record: 0, or why the file is outside the grammar (1 line count, 2 no '@', 3 no '+',
+ *                   4 lengths differ) and the 0-based number of the smallest offending record; the call then fails with a
+ *                   message that names the record from 1.  A text and index that do not fit in free device memory fail
+ *                   with a message naming the bytes.  index_ms / upload_ms: host clock around the index kernels / the
+ *                   upload (inflate included); inflate: the file's entry as msw_alignment_last_inflate reports one.
+ *                   The handle stays usable after every failure.  The object belongs to h: close it before
+ *                   msw_core_destroy(h).
+ * msw_fastq_select  replaces the current selection by the records `ids` names: sorted ascending, every id once (file
+ *                   order).  n == 0 is valid.  An id >= n_records fails the call, which names it and the record count,
+ *                   and leaves the selection as it was.  *n_selected_out: the distinct ids; *bytes_out: their records' bytes.
+ * msw_fastq_next    the next whole records of the selection, at most max_bytes (1 MiB ... 1 GiB) of them, copied verbatim:
+ *                   *out points into a pinned buffer of the handle, valid until the next msw_fastq_* call on it;
+ *                   *len_out == 0: the selection is exhausted.  Every piece ends at a record end; a record longer than
+ *                   max_bytes fails the call (the selection stays where it was).
+ * msw_fastq_next_gzip  the same inside the handle's open gzip stream (msw_core_gzip_begin ... _end): returns the bytes to
+ *                   append to the file, as msw_core_text_block_gzip does; *text_len_out (may be NULL): the plain length.
+ * msw_fastq_last_timing  measurement hook (tools/extract_timing.py): device time of the gather kernel over the pieces since
+ *                   the last msw_fastq_select (events on the handle's stream; copies and the gzip kernels are not in it)
+ *                   and the bytes it wrote.
+ * MSWEEP_HOST_EXTRACT=1 in the environment at msw_fastq_open (developer switch): the file is read and inflated by zlib on
+ * the host and indexed, validated and gathered by plain host loops (msweep_amd/csrc/fastq_host.hpp) behind the same calls,
+ * with the same messages -- the second tool's method, the other side of the A/B and of the tests; msw_fastq_last_timing
+ * then reports the host clock of the gather loop. */
+typedef struct msw_fastq *msw_fastq_t;
+typedef struct msw_fastq_info {
+  uint64_t n_records, text_bytes;
+  int32_t reason;
+  uint64_t bad_record;
+  msw_inflate_info inflate;
+  double index_ms, upload_ms;
+} msw_fastq_info;
+int msw_fastq_open(msw_handle h, const char *path, msw_fastq_t *out, msw_fastq_info *info);
+int msw_fastq_select(msw_handle h, msw_fastq_t fq, const uint32_t *ids, size_t n, uint64_t *n_selected_out,
+                     uint64_t *bytes_out);
+int msw_fastq_next(msw_handle h, msw_fastq_t fq, size_t max_bytes, const char **out, size_t *len_out);
+int msw_fastq_next_gzip(msw_handle h, msw_fastq_t fq, size_t max_bytes, const char **out, size_t *len_out,
+                        size_t *text_len_out);
+int msw_fastq_last_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out);
+void msw_fastq_close(msw_fastq_t fq);
 /* 1: the handle's arrays are device-resident (msw_alignment_read_device served the text with its kernels); 0: host
  * arrays (msw_alignment_read, or the host parser behind the device entry). */
 int msw_alignment_on_device(msw_alignment_t a);

@@ -6,6 +6,8 @@ holds the driver's side).  The matrix outputs -- --write-probs / --print-probs, 
 --compress z (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62) writes them and the bins as `<name>.gz`, the
 gzip stream compressed on the device as well (Core.gzip_begin / text_block_gzip / gzip_append / gzip_end); bz2, lzma
 and zstd are refused, and --compression-level 1 ... 9 all run the core's one parse (0 stores).
+--extract-reads A[,B,...] goes one step further than the bins: `<dir>/<group>_<k>.fastq` holds the binned reads of the k-th
+FASTQ file themselves, gathered on the device where the file lies (Core.fastq_open; extract_reads below).
 Every tab-separated column of the -i file is a grouping of its own: the estimation runs once per column
 (src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several."""
 import argparse
@@ -53,6 +55,8 @@ def parse(argv):
     ap.add_argument("--bin-reads", action="store_true")
     ap.add_argument("--target-groups", type=lambda v: v.split(","))
     ap.add_argument("--min-abundance", type=float)
+    ap.add_argument("--extract-reads", type=lambda v: v.split(","),
+                    help="FASTQ files A[,B,...] (plain, gzip or BGZF): with --bin-reads, <group>_<k>.fastq per target group and file")
     ap.add_argument("--compress", default="plaintext", help="plaintext or z (gzip, written on the device)")
     ap.add_argument("--compression-level", type=int, default=6, help="0 stores; 1 ... 9 run the same parse")
     ap.add_argument("--device", type=int, default=0)
@@ -102,6 +106,11 @@ class GzipOut:
 
     def text_block(self, what, e0, e1, **kw):
         self.f.write(self.core.text_block_gzip(what, e0, e1, **kw))
+
+    def pieces(self, pieces):
+        """bytes the stream has given out already (Fastq.pieces_gzip)"""
+        for z in pieces:
+            self.f.write(z)
 
     def flush(self):
         pass
@@ -244,9 +253,52 @@ def dirichlet_kld_rate(alphas):
     return np.exp(log_kld), np.exp(log_kld - lsum)
 
 
+EXTRACT_PIECE = 256 << 20     # bytes of records per Fastq.pieces call
+
+
+def extract_reads(core, aln, targets, bin_ptr, reads, a):
+    """--extract-reads: for the k-th FASTQ file (from 1) and every target group g, `<dir>/<g>_<k>.fastq` (`.fastq.gz`, one
+    gzip stream, under --compress z) holds the records whose 0-based number in the file is a read id of g's bin, verbatim
+    and in file order; an empty bin gives an empty file.  The files are opened at the first grouping that bins, stay
+    resident on the device for the later ones (a.fastqs) and go with the handle.  Returns the exit status."""
+    try:
+        if not a.fastqs:
+            for path in a.extract_reads:
+                fq = core.fastq_open(path)
+                a.fastqs.append(fq)
+                if a.verbose:
+                    info = fq.info["inflate"]
+                    if info["payload_bytes"] or info["fallback_reason"]:
+                        how = "the device" if info["on_device"] else f"the host ({info['reason']})"
+                        if info["on_device"] and info["n_members"]:
+                            how += f" ({info['n_members']} BGZF members)"
+                        sys.stderr.write(f"note: {path}: gzip input inflated on {how}; {fq.info['n_records']} records\n")
+                    else:
+                        sys.stderr.write(f"note: {path}: plain text; {fq.info['n_records']} records\n")
+        # before any file is written: a read file of another sample has another number of records
+        for path, fq in zip(a.extract_reads, a.fastqs):
+            if fq.info["n_records"] != aln.n_reads:
+                raise RuntimeError(f"{path} holds {fq.info['n_records']} records, the pseudoalignment {aln.n_reads} reads")
+        for k_file, fq in enumerate(a.fastqs, 1):
+            for k, name in enumerate(targets):
+                fq.select(reads[int(bin_ptr[k]):int(bin_ptr[k + 1])])
+                out = binning.extract_path(a.prefix, name, k_file)
+                if a.compress == "z":
+                    with GzipOut(core, out, a.compression_level) as f:     # <dir>/<group>_<k>.fastq.gz
+                        f.pieces(fq.pieces_gzip(EXTRACT_PIECE))
+                else:
+                    with open(out, "wb") as f:
+                        for piece in fq.pieces(EXTRACT_PIECE):
+                            f.write(piece)
+    except (OSError, RuntimeError) as ex:      # (MswError is a RuntimeError)
+        sys.stderr.write(f"Extracting the reads failed:\n  {ex}\nexiting\n")
+        return 1
+    return 0
+
+
 def bin_reads(core, aln, estimated_names, theta, a):
     """--bin-reads (src/mSWEEP.cpp:437-469): targets, thresholds 1 - theta, the bins from the device, one file per
-    target (an empty bin gives an empty file).  Returns the exit status."""
+    target (an empty bin gives an empty file), then --extract-reads.  Returns the exit status."""
     try:
         targets = binning.resolve_targets(estimated_names, a.target_groups)
         if a.min_abundance is not None:
@@ -268,6 +320,8 @@ def bin_reads(core, aln, estimated_names, theta, a):
         except (OSError, MswError) as ex:
             sys.stderr.write(f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
             return 1
+    if a.extract_reads:
+        return extract_reads(core, aln, targets, bin_ptr, reads, a)
     return 0
 
 
@@ -289,6 +343,15 @@ def main(argv=None):
         # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
         sys.stderr.write("Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n")
         return 1
+    if a.extract_reads is not None:
+        # --extract-reads: the bins are its input, and every path names a file
+        if not a.bin_reads:
+            sys.stderr.write("Extracting the reads failed:\n  --extract-reads needs --bin-reads\nexiting\n")
+            return 1
+        if any(not p for p in a.extract_reads):
+            sys.stderr.write("Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n")
+            return 1
+    a.fastqs = []     # the read files of --extract-reads, resident from the first grouping that bins
     def read_indicators():
         # every tab-separated column of -i is a grouping of its own (include/Reference.hpp:67-94); the estimation runs
         # once per column (src/mSWEEP.cpp:282), here from ONE resident alignment
@@ -355,10 +418,14 @@ def main(argv=None):
     # the grouping loop (src/mSWEEP.cpp:282): build, outputs, solve, bins, bootstrap per column on the one handle -- every
     # build replaces the resident likelihood and all that was derived from the one before (include/msweep_core.h).  A
     # grouping that fails ends the run; the files of the groupings before it stay.
-    for index, grouping in enumerate(groupings):
-        rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
-        if rc:
-            return rc
+    try:
+        for index, grouping in enumerate(groupings):
+            rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
+            if rc:
+                return rc
+    finally:
+        for fq in list(a.fastqs):      # --extract-reads: the read files go at the end of the run
+            fq.close()
     core.close()
     return 0
 

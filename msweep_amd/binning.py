@@ -47,6 +47,12 @@ def bin_path(prefix, name):
     return d + "/" + name + ".bin"
 
 
+def extract_path(prefix, name, k):
+    """--extract-reads: the reads of target group `name` from the k-th FASTQ file (k from 1), beside the bins:
+    <dir>/<name>_<k>.fastq.  This project's own rule [UPSTREAM-UNVERIFIED]: mGEMS is not vendored by the reference."""
+    return bin_path(prefix, name)[:-len(".bin")] + f"_{k}.fastq"
+
+
 def format_ids(ids):
     """One decimal id per line, each line ending in '\\n' (mGEMS::WriteBin), formatted with array operations:
     10 M ids in well under a second."""

@@ -39,6 +39,7 @@ EXPORTS = [
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
     "msw_core_inflate_gzip", "msw_alignment_last_inflate",
     "msw_core_set_dense_logl_file", "msw_core_set_dense_logl_text", "msw_core_likfile_counts",
+    "msw_fastq_open", "msw_fastq_select", "msw_fastq_next", "msw_fastq_next_gzip", "msw_fastq_last_timing", "msw_fastq_close",
 ]
 
 # msw_inflate_info.fallback_reason
@@ -77,6 +78,22 @@ class LikFileInfo(C.Structure):
         d = {name: getattr(self, name) for name, _ in self._fields_ if name != "inflate"}
         d["inflate"] = self.inflate.as_dict()
         d["reason_text"] = LIKFILE_REASONS[self.reason] if 0 <= self.reason < len(LIKFILE_REASONS) else "?"
+        return d
+
+
+# msw_fastq_info.reason
+FASTQ_REASONS = ("none", "line count", "no '@'", "no '+'", "lengths differ")
+
+
+class FastqInfo(C.Structure):
+    """msw_fastq_info: what Core.fastq_open found -- records, bytes of text, how the file was inflated, the stage times"""
+    _fields_ = [("n_records", C.c_uint64), ("text_bytes", C.c_uint64), ("reason", C.c_int32), ("bad_record", C.c_uint64),
+                ("inflate", InflateInfo), ("index_ms", C.c_double), ("upload_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "inflate"}
+        d["inflate"] = self.inflate.as_dict()
+        d["reason_text"] = FASTQ_REASONS[self.reason] if 0 <= self.reason < len(FASTQ_REASONS) else "?"
         return d
 
 
@@ -177,6 +194,13 @@ def load_library():
     L.msw_core_last_gzip_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.msw_core_inflate_gzip.argtypes = [vp, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(InflateInfo)]
     L.msw_alignment_last_inflate.argtypes = [vp, C.POINTER(InflateInfo), sz, C.POINTER(sz)]
+    L.msw_fastq_open.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(FastqInfo)]
+    L.msw_fastq_select.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.msw_fastq_next.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.msw_fastq_next_gzip.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.msw_fastq_last_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64)]
+    L.msw_fastq_close.argtypes = [vp]
+    L.msw_fastq_close.restype = None
     L.msw_core_trace.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.msw_core_set_trace_theta.argtypes = [vp, sz]
     L.msw_core_bootstrap.argtypes = [vp, vp, C.c_int32, sz, sz, sz, vp, dp, sz, C.c_int, C.c_int, vp, vp]
@@ -310,6 +334,65 @@ def _alignment_views(L, h, owner, n_ecs, n_hits, n_aligned, n_reads):
                 ec_reads=view(p[4], n_aligned, C.c_uint32, np.uint32), n_reads=int(n_reads))
 
 
+class Fastq:
+    """A read file resident on a Core's device with the index of its records (msw_fastq_open): select read ids, then take
+    their records in pieces -- plain bytes, or bytes of the handle's open gzip stream.  Closed by close(), or with its
+    Core."""
+
+    def __init__(self, core, h, info):
+        self._core, self._h, self.info = core, h, info
+
+    def _handle(self):
+        if not self._h or not self._core._h:
+            raise MswError("the read file is closed")
+        return self._h
+
+    def select(self, ids):
+        """Replaces the selection by the records `ids` names (0-based, any order, repeats allowed): ascending, each once.
+        Returns (distinct records, their bytes)."""
+        ids = _arr(ids, np.uint32)
+        if ids.ndim != 1:
+            raise MswError("Fastq.select: ids must be a 1-D array")
+        n, nb = C.c_uint64(), C.c_uint64()
+        c = self._core
+        c._check(c._L.msw_fastq_select(c._h, self._handle(), _ptr(ids) if len(ids) else None, len(ids), C.byref(n), C.byref(nb)))
+        return n.value, nb.value
+
+    def pieces(self, max_bytes=256 << 20):
+        """The selection's records in file order, whole records in pieces of at most max_bytes (msw_fastq_next)."""
+        c = self._core
+        while True:
+            p, n = C.c_void_p(), C.c_size_t()
+            c._check(c._L.msw_fastq_next(c._h, self._handle(), int(max_bytes), C.byref(p), C.byref(n)))
+            if not n.value:
+                return
+            yield C.string_at(p.value, n.value)
+
+    def pieces_gzip(self, max_bytes=256 << 20):
+        """The same inside the Core's open gzip stream (msw_fastq_next_gzip): per piece the bytes to append to the file
+        (zlib on the host, MSWEEP_HOST_GZIP=1, may hold a piece's bytes back: b"")."""
+        c = self._core
+        while True:
+            p, n, nt = C.c_void_p(), C.c_size_t(), C.c_size_t()
+            c._check(c._L.msw_fastq_next_gzip(c._h, self._handle(), int(max_bytes), C.byref(p), C.byref(n), C.byref(nt)))
+            if not nt.value:
+                return
+            yield C.string_at(p.value, n.value) if n.value else b""
+
+    def close(self):
+        if self._h and self._core._h:
+            self._core._L.msw_fastq_close(self._h)
+        self._h = None
+        if self in self._core._fastqs:
+            self._core._fastqs.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -329,9 +412,12 @@ class Core:
             raise MswError(self._L.msw_last_error(None).decode())
         self.device = device
         self.generation = 0     # solves started on this handle (rcgpar.EcProbs: whose state gamma() would read)
+        self._fastqs = []       # read files open on this handle (fastq_open): closed with it
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            for fq in list(getattr(self, "_fastqs", [])):
+                fq.close()
             self._L.msw_core_destroy(self._h)
             self._h = None
 
@@ -602,6 +688,24 @@ class Core:
         ms, ni, no = C.c_double(), C.c_uint64(), C.c_uint64()
         self._check(self._L.msw_core_last_gzip_timing(self._h, C.byref(ms), C.byref(ni), C.byref(no)))
         return ms.value, ni.value, no.value
+
+    # ---- --extract-reads: the records of a FASTQ file by read id (msw_fastq_*)
+    def fastq_open(self, path):
+        """A read file -- plain, gzip or BGZF -- resident on the device with its record index: a Fastq with .info
+        (msw_fastq_info as a dict), .select(ids), .pieces(max_bytes), .pieces_gzip(max_bytes), .close().  A file outside
+        the strict four-line grammar raises MswError naming the record."""
+        h, info = C.c_void_p(), FastqInfo()
+        self._check(self._L.msw_fastq_open(self._h, os.fsencode(path), C.byref(h), C.byref(info)))
+        fq = Fastq(self, h, info.as_dict())
+        self._fastqs.append(fq)
+        return fq
+
+    def last_fastq_timing(self):
+        """(ms of the gather over the pieces since the last Fastq.select -- device events; the host clock under
+        MSWEEP_HOST_EXTRACT=1 --, bytes gathered)"""
+        ms, nb = C.c_double(), C.c_uint64()
+        self._check(self._L.msw_fastq_last_timing(self._h, C.byref(ms), C.byref(nb)))
+        return ms.value, nb.value
 
     # ---- gzip input inflated on the device (msw_core_inflate_gzip: the decoder's test and diagnostic entry)
     def inflate_gzip(self, data, chunk_bytes=0):

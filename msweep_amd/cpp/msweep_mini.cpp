@@ -13,6 +13,8 @@
 // --compress z / --compression-level (src/mSWEEP.cpp:107-109, src/OutfileDesignator.cpp:30-62: the matrix outputs and the
 // bins as `<name>.gz`, the gzip stream compressed on the device, msw_core_gzip_*; bz2, lzma and zstd are refused).  Same flags and messages as the reference for what it covers; held byte-for-byte against
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
+// --extract-reads A[,B,...] (with --bin-reads): `<dir>/<group>_<k>.fastq[.gz]`, the binned reads of the k-th FASTQ file
+// themselves, gathered on the device where the file lies (msw_fastq_*; the step docs/pipeline.md:59-64 gives to mGEMS).
 // Every tab-separated column of the -i file is a grouping of its own and the whole estimation runs once per column
 // (src/mSWEEP.cpp:282) -- from ONE read of the pseudoalignment, whose classes stay in device memory: run_grouping() is the
 // body of that loop, out_path() names its files (`<prefix>_<i>_...` when there are several; tests/test_gpu_groupings.py).
@@ -56,6 +58,8 @@ struct Args {
   bool bin_reads = false, have_target_groups = false, have_min_abundance = false;
   std::vector<std::string> target_groups;
   double min_abundance = 0.0;
+  bool have_extract_reads = false;
+  std::vector<std::string> extract_reads;  // --extract-reads A[,B,...]: the FASTQ files the bins are extracted from
   std::string compress = "plaintext";  // or "z"
   int compression_level = 6;           // 0 stores; 1 ... 9 run the core's one parse
 };
@@ -111,6 +115,17 @@ Args parse(int argc, char **argv) {
     else if (k == "--target-groups") {
       a.target_groups = split(val(), ',');
       a.have_target_groups = true;
+    } else if (k == "--extract-reads") {
+      // (every element counts, an empty one too: main() refuses it)
+      const std::string v = val();
+      a.extract_reads.clear();
+      for (size_t b = 0;;) {
+        const size_t e = v.find(',', b);
+        a.extract_reads.push_back(v.substr(b, e == std::string::npos ? e : e - b));
+        if (e == std::string::npos) break;
+        b = e + 1;
+      }
+      a.have_extract_reads = true;
     } else if (k == "--min-abundance") {
       a.min_abundance = std::stod(val());
       a.have_min_abundance = true;
@@ -223,6 +238,17 @@ class Out {
     }
   }
   void write(const std::string &s) { write(s.data(), s.size()); }
+  // the selection of a read file, whole records in pieces of at most max_bytes (msw_fastq_next / _next_gzip)
+  void records(msw_fastq_t fq, size_t max_bytes) {
+    for (;;) {
+      const char *p = nullptr;
+      size_t n = 0, n_text = 0;
+      if (gz_) check(h_, msw_fastq_next_gzip(h_, fq, max_bytes, &p, &n, &n_text));
+      else check(h_, msw_fastq_next(h_, fq, max_bytes, &p, &n));
+      if (!(gz_ ? n_text : n)) break;
+      os_->write(p, (std::streamsize)n);
+    }
+  }
   void text_block(int what, size_t e0, size_t e1, const uint64_t *prefix, size_t n_zero) {
     const char *p = nullptr;
     size_t n = 0;
@@ -230,6 +256,7 @@ class Out {
     else check(h_, msw_core_text_block(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr));
     os_->write(p, (std::streamsize)n);
   }
+  bool good() const { return (bool)*os_; }
   void close() {
     if (open_) {
       open_ = false;
@@ -291,6 +318,18 @@ void read_likelihood_file(msw_handle h, const std::string &path, size_t G, std::
   for (size_t j = 0; j < E; ++j)
     for (size_t g = 0; g < G; ++g) L[g * E + j] = cols[j][g];
 }
+
+// what the groupings of one run share: the handle and the alignment read once in front of the loop
+struct Run {
+  msw_handle h = nullptr;
+  msw_alignment_t aln = nullptr;
+  size_t n_ecs = 0, n_reads = 0, n_groupings = 1;
+  std::vector<uint64_t> ec_counts;
+  int algo = MSW_ALGO_RCG, prec = MSW_PREC_DOUBLE;
+  // --extract-reads: the read files, opened at the first grouping that bins, and their record counts
+  mutable std::vector<msw_fastq_t> fastqs;
+  mutable std::vector<uint64_t> fastq_records;
+};
 
 // ---- --bin-reads (src/mSWEEP.cpp:437-469; the same choices as msweep_amd/binning.py) ---------------------------------
 struct BinningError : std::runtime_error {
@@ -363,10 +402,68 @@ std::string write_bin(const std::string &path, const uint32_t *ids, size_t n) {
   return err;
 }
 
+// --extract-reads: for the k-th FASTQ file (from 1) and every target group g, `<dir>/<g>_<k>.fastq` (`.fastq.gz`, one gzip
+// stream, under --compress z) holds the records whose 0-based number in the file is a read id of g's bin, verbatim and in
+// file order; an empty bin gives an empty file.  The files are opened at the first grouping that bins and stay resident on
+// the device for the later ones (`fastqs`; main() closes them).  The same calls as msweep_amd/__main__.py extract_reads.
+// Returns the exit status.
+int extract_reads(const Args &a, msw_handle h, size_t n_reads, std::vector<msw_fastq_t> &fastqs, std::vector<uint64_t> &fastq_records,
+                  const std::vector<std::string> &names, const std::vector<uint64_t> &bin_ptr, const std::vector<uint32_t> &reads) {
+  constexpr size_t kPiece = (size_t)256 << 20;  // bytes of records per call
+  try {
+    if (fastqs.empty()) {
+      static const char *const why[] = {"none", "forced", "header", "probe mismatch", "chunk status", "crc", "trailing bytes", "memory", "long span"};
+      for (const std::string &path : a.extract_reads) {
+        msw_fastq_t fq = nullptr;
+        msw_fastq_info info;
+        check(h, msw_fastq_open(h, path.c_str(), &fq, &info));
+        fastqs.push_back(fq);
+        fastq_records.push_back(info.n_records);
+        if (a.verbose) {
+          const msw_inflate_info &f = info.inflate;
+          std::cerr << "note: " << path << ": ";
+          if (!f.payload_bytes && !f.fallback_reason) std::cerr << "plain text";
+          else if (f.on_device && f.n_members) std::cerr << "gzip input inflated on the device (" << f.n_members << " BGZF members)";
+          else if (f.on_device) std::cerr << "gzip input inflated on the device";
+          else std::cerr << "gzip input inflated on the host (" << why[f.fallback_reason >= 0 && f.fallback_reason < 9 ? f.fallback_reason : 0] << ")";
+          std::cerr << "; " << info.n_records << " records\n";
+        }
+      }
+    }
+    // before any file is written: a read file of another sample has another number of records
+    for (size_t i = 0; i < fastqs.size(); ++i)
+      if (fastq_records[i] != n_reads)
+        throw std::runtime_error(a.extract_reads[i] + " holds " + std::to_string(fastq_records[i]) + " records, the pseudoalignment " +
+                                 std::to_string(n_reads) + " reads");
+    for (size_t i = 0; i < fastqs.size(); ++i)
+      for (size_t k = 0; k < names.size(); ++k) {
+        check(h, msw_fastq_select(h, fastqs[i], reads.data() + bin_ptr[k], bin_ptr[k + 1] - bin_ptr[k], nullptr, nullptr));
+        const std::string bin = bin_path(a.prefix, names[k]);
+        const std::string path = bin.substr(0, bin.size() - 4) + "_" + std::to_string(i + 1) + ".fastq";
+        const bool gz = a.compress == "z";
+        Out f(h, path, gz, a.compression_level);
+        if (!gz && !f.good()) throw std::runtime_error("cannot open " + path);
+        f.records(fastqs[i], kPiece);
+        f.close();
+        if (!f.good()) throw std::runtime_error("cannot write " + path);
+      }
+  } catch (const std::exception &ex) {
+    std::cerr << "Extracting the reads failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  return 0;
+}
+
+int extract_after_bins(const Args &a, msw_handle h, const Run &r, const std::vector<std::string> &names,
+                       const std::vector<uint64_t> &bin_ptr, const std::vector<uint32_t> &reads) {
+  if (!a.have_extract_reads) return 0;
+  return extract_reads(a, h, r.n_reads, r.fastqs, r.fastq_records, names, bin_ptr, reads);
+}
+
 // the bins from the device and one file per target (an empty bin: an empty file), written on up to writer_threads()
-// threads; returns the exit status
+// threads, then --extract-reads; returns the exit status
 int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vector<std::string> &est,
-              const std::vector<double> &theta) {
+              const std::vector<double> &theta, const Run &r) {
   std::vector<std::string> names;
   std::vector<uint64_t> bin_ptr;
   std::vector<uint32_t> reads;
@@ -403,7 +500,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
         return 1;
       }
     }
-    return 0;
+    return extract_after_bins(a, h, r, names, bin_ptr, reads);
   }
   std::vector<std::thread> pool;
   for (size_t t = 0; t < nt; ++t)
@@ -417,7 +514,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
       std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
       return 1;
     }
-  return 0;
+  return extract_after_bins(a, h, r, names, bin_ptr, reads);
 }
 
 // MSWEEP_HOST_TEXT=1 (developer switch): the matrices come to the host as doubles and are formatted here, cell by cell,
@@ -581,15 +678,6 @@ void dirichlet_kld_rate(const std::vector<double> &alphas, std::vector<double> &
   }
 }
 
-// what the groupings of one run share: the handle and the alignment read once in front of the loop
-struct Run {
-  msw_handle h = nullptr;
-  msw_alignment_t aln = nullptr;
-  size_t n_ecs = 0, n_reads = 0, n_groupings = 1;
-  std::vector<uint64_t> ec_counts;
-  int algo = MSW_ALGO_RCG, prec = MSW_PREC_DOUBLE;
-};
-
 // Everything main() does per grouping column -- the body of the loop at src/mSWEEP.cpp:282-563: the device build with
 // this column's indicators (it replaces the resident likelihood and all that was derived from the one before,
 // include/msweep_core.h), the likelihood outputs, the solve, the bins, the bootstrap, the probabilities and the
@@ -696,7 +784,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
     results.push_back(theta);
     if (a.bin_reads) {
       // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
-      if (bin_reads(a, h, r.aln, est_names, theta) != 0) return 1;
+      if (bin_reads(a, h, r.aln, est_names, theta, r) != 0) return 1;
     }
     if (a.iters > 0) {
       // every grouping's bootstrap starts the stream from the same seed (the reference constructs the sample inside its
@@ -802,6 +890,18 @@ int main(int argc, char **argv) {
     std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
     return 1;
   }
+  if (a.have_extract_reads) {
+    // --extract-reads: the bins are its input, and every path names a file
+    if (!a.bin_reads) {
+      std::cerr << "Extracting the reads failed:\n  --extract-reads needs --bin-reads\nexiting\n";
+      return 1;
+    }
+    for (const std::string &p : a.extract_reads)
+      if (p.empty()) {
+        std::cerr << "Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n";
+        return 1;
+      }
+  }
   // every tab-separated column of -i is a grouping of its own; the estimation runs once per column
   // (src/mSWEEP.cpp:282), here from ONE resident alignment
   std::vector<Grouping> groupings;
@@ -883,6 +983,7 @@ int main(int argc, char **argv) {
   for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(a, r, groupings[i], i);
   // (the pseudoalignment goes at the end: device memory given back is scrubbed before it is handed out again, and the
   // solver state is allocated after the build)
+  for (msw_fastq_t fq : r.fastqs) msw_fastq_close(fq);
   msw_alignment_destroy(r.aln);
   msw_core_destroy(h);
   return rc;

@@ -23,6 +23,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
@@ -44,6 +45,8 @@
 #include "inflate_kernels.hpp"
 #include "inflate_member_kernels.hpp"
 #include "likelihood_text_kernels.hpp"
+#include "fastq_host.hpp"
+#include "fastq_kernels.hpp"
 
 using namespace msw;
 
@@ -261,6 +264,19 @@ struct InflateState {
   }
 };
 
+// ---- --extract-reads: what the msw_fastq_* calls keep on the handle (host_fastq.inc); the text and the index of a read
+// file live in its own msw_fastq ---------------------------------------------------------------------------------------
+struct FastqState {
+  PinnedBuf pinned{"msw_fastq_next", "the records"};
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the gather kernel
+  double kernel_ms = 0.0;                 // of the pieces since the last msw_fastq_select (msw_fastq_last_timing)
+  uint64_t bytes = 0;
+  ~FastqState() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -280,6 +296,7 @@ struct msw_core {
   TextState text;
   GzState gz;
   InflateState inf;
+  FastqState fastq;
   std::vector<uint64_t> lik_counts;  // first column of the last served likelihood file (host_likelihood_file.inc)
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
@@ -1079,6 +1096,7 @@ struct StageTimer {
 #include "host_bin.inc"
 #include "host_text.inc"
 #include "host_gzip.inc"
+#include "host_fastq.inc"
 
 // =========================================================================================
 // C ABI
@@ -1360,6 +1378,32 @@ int msw_core_last_gzip_timing(msw_handle h, double *kernel_ms_out, uint64_t *byt
     if (bytes_out_out) *bytes_out_out = h->gz.bytes_out;
   });
 }
+
+// ---- --extract-reads: the records of a FASTQ file by read id (host_fastq.inc) ------------------------------------------------
+int msw_fastq_open(msw_handle h, const char *path, msw_fastq_t *out, msw_fastq_info *info) {
+  return guarded(h, [&] { fastq_open_impl(h, path, out, info); });
+}
+
+int msw_fastq_select(msw_handle h, msw_fastq_t fq, const uint32_t *ids, size_t n, uint64_t *n_selected_out, uint64_t *bytes_out) {
+  return guarded(h, [&] { fastq_select_impl(h, fq, ids, n, n_selected_out, bytes_out); });
+}
+
+int msw_fastq_next(msw_handle h, msw_fastq_t fq, size_t max_bytes, const char **out, size_t *len_out) {
+  return guarded(h, [&] { fastq_next_impl(h, fq, max_bytes, false, out, len_out, nullptr); });
+}
+
+int msw_fastq_next_gzip(msw_handle h, msw_fastq_t fq, size_t max_bytes, const char **out, size_t *len_out, size_t *text_len_out) {
+  return guarded(h, [&] { fastq_next_impl(h, fq, max_bytes, true, out, len_out, text_len_out); });
+}
+
+int msw_fastq_last_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out) {
+  return guarded(h, [&] {
+    if (kernel_ms_out) *kernel_ms_out = h->fastq.kernel_ms;
+    if (bytes_out) *bytes_out = h->fastq.bytes;
+  });
+}
+
+void msw_fastq_close(msw_fastq_t fq) { fastq_close_impl(fq); }
 
 int msw_core_last_text_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out) {
   return guarded(h, [&] {

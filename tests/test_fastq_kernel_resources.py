@@ -1,0 +1,45 @@
+"""CPU (hipcc cross-compiles without a GPU): the kernels host_fastq.inc launches (fastq_kernels.hpp: the record index, the
+validation and the gather of --extract-reads) run without scratch memory -- the gather assembles the 16 bytes of a vector
+that crosses a record end in four registers, and an indexed local array would show up here as scratch -- and hold a few
+words of LDS at most.  Compiled in a translation unit of their own, as tests/test_deflate_kernel_resources.py does."""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+TU = r'''
+#include "fastq_kernels.hpp"
+'''
+
+KERNELS = ("k_fq_count", "k_fq_index", "k_fq_validate", "k_fq_gather")
+
+
+def test_fastq_kernels_have_no_scratch(tmp_path):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    src = tmp_path / "fq.hip"
+    src.write_text(TU)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
+                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "fq.o")],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res, cur = {}, None
+    for ln in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = m.group(1)
+            res[cur] = {}
+            continue
+        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
+        if m and cur:
+            res[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+    # every kernel host_fastq.inc launches is one of these
+    inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_fastq.inc")).read()
+    launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))
+    assert launched == set(KERNELS), launched
+    for frag in KERNELS:
+        hit = {k: v for k, v in res.items() if frag in k}
+        assert len(hit) == 1, (frag, sorted(res))
+        for v in hit.values():
+            assert v["ScratchSize"] == 0, hit
+            assert v["LDS Size"] <= 64, hit
