@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from .buildlib import source_hash  # (sha256 prefix over the library's sources: one definition, buildlib.py)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MSWEEP_CORE_LIB: developer override for A/B timing of two builds in one job
 LIB_PATH = os.environ.get("MSWEEP_CORE_LIB") or os.path.join(_HERE, "libmsweep_core.so")
@@ -119,18 +121,6 @@ class BootstrapTiming(C.Structure):
 
 
 _lib = None
-
-
-def source_hash():
-    """sha256 prefix over the library's sources (the same function as __graft_entry__.source_hash)."""
-    import hashlib
-    csrc = os.path.join(_HERE, "csrc")
-    h = hashlib.sha256()
-    files = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc", ".h")))
-    for f in files + [os.path.join(os.path.dirname(_HERE), "include", "msweep_core.h")]:
-        h.update(os.path.basename(f).encode() + b"\0")
-        h.update(open(f, "rb").read())
-    return h.hexdigest()[:16]
 
 
 def _check_fresh(L):

@@ -2,6 +2,7 @@
 // ids of every target group's bin, without the G x E responsibility matrix anywhere.
 #pragma once
 #include "gamma_kernels.hpp"
+#include "prim_ops.hpp"
 
 namespace msw {
 
@@ -103,13 +104,7 @@ __global__ __launch_bounds__(256) void k_bin_write(SellDev S, double a, double l
   }
 }
 
-// read count of the i-th sorted pair (0 for the spare element i = n: the exclusive scan's total)
-struct BinPairLen {
-  const uint32_t *ec;
-  const uint64_t *rptr;
-  size_t n;
-  __host__ __device__ uint64_t operator()(size_t i) const { return i < n ? rptr[ec[i] + 1] - rptr[ec[i]] : 0; }
-};
+// (BinPairLen, the read count of the i-th sorted pair: prim_ops.hpp)
 
 // bin_ptr[k] = output offset of the first pair of slot k (k = n_targets: the total); keys sorted ascending
 __global__ __launch_bounds__(256) void k_bin_ptr(const uint32_t *key, size_t n, const uint64_t *roff, uint32_t n_targets,

@@ -116,6 +116,10 @@ __device__ unsigned long long g_stamps[64 * 40];
 struct TabDev {
   double2 *A, *B;
 };
+// slot areas of up to this many entries are rebuilt by the single workgroup of k_finstep / k_prepB; larger ones by
+// k_tables (state_kernels.hpp)
+constexpr int kTabInline = 16384;
+constexpr int kStepRegs = 6;  // groups per thread the register paths of k_finstep / k_em_fin hold (6144 groups; more: the looping paths)
 
 // Scalar state of one solve; lives in device memory, mirrored to pinned host memory when
 // the host polls.  Kept POD.

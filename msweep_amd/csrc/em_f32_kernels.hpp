@@ -18,7 +18,7 @@
 // Per cell: 2 ds_read_b32 + 1 ds_add_u64 against ds_read_b64 + ds_read_b128 + ds_add_u64, ~7 instead of ~11 vector
 // operations, no second table column (EM's objective has no entropy term).
 //
-// Served layouts (msweep_core.hip em_f32_layout_ok), one GPU, at most kStepRegs * 1024 = 6144 groups, any EC length
+// Served layouts (sweep_dense.hip em_f32_layout_ok), one GPU, at most kStepRegs * 1024 = 6144 groups, any EC length
 // (slice classes, wavefront-per-EC), the group vectors in LDS:
 //   * 4-byte offset records with the whole fp64 slot table in LDS (k_em_passB_f32);
 //   * index records -- the layouts whose fp64 slot table does NOT fit LDS beside the group vectors and is kept as the

@@ -15,6 +15,7 @@
 #pragma once
 #include "common.hpp"
 #include "reader_kernels.hpp"
+#include "prim_ops.hpp"
 
 namespace msw {
 
@@ -87,17 +88,7 @@ __global__ void k_fq_validate(const unsigned char *txt, const uint64_t *line_off
   if (mine != kFqNoBad) atomicMin(bad, mine);
 }
 
-// length of the i-th selected record; i == m: the spare zero behind them (the scan's total)
-struct FqLen {
-  const uint32_t *ids;
-  const uint64_t *rec_off;
-  size_t m;
-  __host__ __device__ uint64_t operator()(size_t i) const {
-    if (i >= m) return 0;
-    const uint64_t id = ids[i];
-    return rec_off[id + 1] - rec_off[id];
-  }
-};
+// (FqLen, the length of the i-th selected record: prim_ops.hpp)
 
 // the largest r in [lo, hi) with off[r] <= D, given off[lo] <= D (at most 64 steps: hi - lo halves)
 __device__ __forceinline__ uint64_t fq_find(const uint64_t *off, uint64_t lo, uint64_t hi, uint64_t D) {

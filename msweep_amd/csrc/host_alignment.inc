@@ -20,50 +20,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
-// vectors whose resize() leaves new elements uninitialised: the large arrays of the reader are written in full by the
-// worker threads right after they are sized -- a zero fill by the sizing thread would be one more serial pass over
-// (and first touch of) hundreds of megabytes
-template <class T>
-struct uninit_alloc : std::allocator<T> {
-  template <class U> struct rebind { using other = uninit_alloc<U>; };
-  uninit_alloc() = default;
-  template <class U> uninit_alloc(const uninit_alloc<U> &) {}
-  template <class U> void construct(U *p) noexcept { ::new (static_cast<void *>(p)) U; }
-  template <class U, class... A> void construct(U *p, A &&...a) { ::new (static_cast<void *>(p)) U(std::forward<A>(a)...); }
-};
-template <class T> using uvec = std::vector<T, uninit_alloc<T>>;
-
-struct msw_alignment {
-  size_t n_targets = 0, n_queries = 0;
-  std::vector<uint64_t> ec_tptr, ec_counts, ec_rptr;
-  uvec<uint32_t> ec_targets, ec_reads;
-  // msw_alignment_read_device (host_reader.inc): the same five arrays in device memory; the host vectors above are
-  // filled from them by the first accessor that needs them (to_host)
-  bool on_device = false;
-  unsigned host_have = 31u;    // which of the five host vectors are filled (bit k: kAln* below); the host reader: all
-  int device = 0;
-  size_t E = 0, H = 0, K = 0;  // classes, their target hits, aligned reads
-  DevBuf<uint64_t> d_tptr, d_counts, d_rptr;
-  DevBuf<uint32_t> d_targets, d_reads;
-  enum : unsigned { kAlnTptr = 1u, kAlnTargets = 2u, kAlnCounts = 4u, kAlnRptr = 8u, kAlnReads = 16u };
-  void to_host(unsigned want) {
-    const unsigned need = want & ~host_have;
-    if (!need) return;
-    MSW_HIP(hipSetDevice(device));
-    auto fetch = [&](unsigned bit, auto &vec, const auto *src, size_t n) {
-      if (!(need & bit)) return;
-      vec.resize(n);
-      if (n) MSW_HIP(hipMemcpy(vec.data(), src, n * sizeof(*src), hipMemcpyDeviceToHost));
-    };
-    fetch(kAlnTptr, ec_tptr, d_tptr.p, E + 1);
-    fetch(kAlnTargets, ec_targets, d_targets.p, H);
-    fetch(kAlnCounts, ec_counts, d_counts.p, E);
-    fetch(kAlnRptr, ec_rptr, d_rptr.p, E + 1);
-    fetch(kAlnReads, ec_reads, d_reads.p, K);
-    host_have |= need;
-  }
-};
-
+// (msw_alignment and its uninitialised vectors: handle.hpp)
 namespace {
 
 thread_local std::string g_aln_error;

@@ -1,4 +1,4 @@
-// host_bin.inc -- msw_core_bin_reads / _aln (included by msweep_core.hip): the mGEMS binning step of
+// host_bin.inc -- msw_core_bin_reads / _aln (included by build.hip): the mGEMS binning step of
 // src/mSWEEP.cpp:437-469 on the device (bin_kernels.hpp).  Device memory: O(E) (lse, counts, offsets) plus
 // O(pairs) (one (target slot, EC) pair per passing EC and target) plus the output; nothing is sized G x E or
 // n_targets x E, and the output is sized from the count pass before it is allocated.  No atomics: every order is
@@ -135,12 +135,11 @@ void bin_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads, si
   MSW_HIP(hipMemsetAsync(cnt.p + E, 0, sizeof(uint32_t), st));
   if (lds) launch_bin_enc<true>(h, gs, B, lse_p.p, cnt.p, nullptr, nullptr, nullptr, false);
   else launch_bin_enc<false>(h, gs, B, lse_p.p, cnt.p, nullptr, nullptr, nullptr, false);
-  auto cnt64 = rocprim::make_transform_iterator(cnt.p, U32ToU64{});
   size_t tmp_bytes = 0;
-  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, cnt64, off.p, (uint64_t)0, (size_t)E + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(prim_scan(nullptr, tmp_bytes, cnt.p, off.p, (size_t)E + 1, st));
   DevBuf<uint8_t> tmp;
   bin_alloc(tmp, tmp_bytes, "scan storage");
-  MSW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, cnt64, off.p, (uint64_t)0, (size_t)E + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(prim_scan(tmp.p, tmp_bytes, cnt.p, off.p, (size_t)E + 1, st));
   uint64_t n_pairs = 0;
   MSW_HIP(hipMemcpyAsync(&n_pairs, off.p + E, sizeof n_pairs, hipMemcpyDeviceToHost, st));
   MSW_HIP(hipStreamSynchronize(st));
@@ -156,18 +155,18 @@ void bin_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads, si
   else launch_bin_enc<false>(h, gs, B, lse_p.p, nullptr, off.p, key.p, val.p, true);
   unsigned bits = 1;
   while (bits < 32 && ((size_t)1 << bits) < n_targets) ++bits;
-  MSW_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)n_pairs, 0u, bits, st));
+  MSW_HIP(prim_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)n_pairs, bits, st));
   bin_alloc(tmp, tmp_bytes, "sort storage");
-  MSW_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)n_pairs, 0u, bits, st));
+  MSW_HIP(prim_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)n_pairs, bits, st));
 
   // output offsets of the sorted pairs (roff[n_pairs] = the reads in all bins) and bin_ptr
   DevBuf<uint64_t> roff, d_bin_ptr;
   bin_alloc(roff, n_pairs + 1, "the output offsets");
   bin_alloc(d_bin_ptr, n_targets + 1, "bin_ptr");
-  auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), BinPairLen{val2.p, d_rptr, (size_t)n_pairs});
-  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, lens, roff.p, (uint64_t)0, (size_t)n_pairs + 1, rocprim::plus<uint64_t>(), st));
+  const BinPairLen lens{val2.p, d_rptr, (size_t)n_pairs};
+  MSW_HIP(prim_scan(nullptr, tmp_bytes, lens, roff.p, (size_t)n_pairs + 1, st));
   bin_alloc(tmp, tmp_bytes, "scan storage");
-  MSW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, lens, roff.p, (uint64_t)0, (size_t)n_pairs + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(prim_scan(tmp.p, tmp_bytes, lens, roff.p, (size_t)n_pairs + 1, st));
   hipLaunchKernelGGL(k_bin_ptr, dim3((unsigned)((n_targets + 1 + 255) / 256)), dim3(256), 0, st, key2.p, (size_t)n_pairs,
                      roff.p, (uint32_t)n_targets, d_bin_ptr.p);
   MSW_HIP(hipGetLastError());

@@ -1,4 +1,4 @@
-// host_bootstrap.inc -- bootstrap driver (included by msweep_core.hip): replaces
+// host_bootstrap.inc -- bootstrap driver (included by solve.hip): replaces
 // BootstrapSample::init_bootstrap / resample_counts (src/BootstrapSample.cpp:33-73) and the
 // replicate loop of main() (src/mSWEEP.cpp:496-518).
 namespace {

@@ -1,5 +1,5 @@
 // host_build.inc -- device build of the likelihood from the pseudoalignment (included by
-// msweep_core.hip): replaces LL_WOR21::fill_ll_mat + fill_ec_counts
+// build.hip): replaces LL_WOR21::fill_ll_mat + fill_ec_counts
 // (include/Likelihood.hpp:109-195).  K0-K2 run on the device; the host computes the O(G) mask /
 // size-class bookkeeping; the SELL-64 packing runs on the device too (pack_kernels.hpp).
 namespace {

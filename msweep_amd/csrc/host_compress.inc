@@ -1,4 +1,4 @@
-// host_compress.inc -- msw_core_set_dense_logl's fast path (included by msweep_core.hip): the
+// host_compress.inc -- msw_core_set_dense_logl's fast path (included by build.hip): the
 // matrix the reference hands to rcg_optl (src/mSWEEP.cpp:194-202, built by
 // include/Likelihood.hpp:176-185) holds log(zi) in every cell whose EC does not hit the group and
 // one of a few lookup-table values elsewhere.  When the staged matrix has that shape it is
@@ -40,7 +40,7 @@ bool compress_dense(msw_core *h, const double *Lm, size_t ld, const double *stag
       DevBuf<double> d_val;
       d_at.upload(at.data(), n, h->stream);
       d_val.alloc(n);
-      hipLaunchKernelGGL(k_lik_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, stage, d_at.p, (uint32_t)n, d_val.p);
+      lik_gather_launch(h->stream, stage, d_at.p, (uint32_t)n, d_val.p);  // (k_lik_gather: input.hip)
       MSW_HIP(hipGetLastError());
       MSW_HIP(hipMemcpyAsync(val.data(), d_val.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
       MSW_HIP(hipStreamSynchronize(h->stream));
@@ -93,10 +93,10 @@ bool compress_dense(msw_core *h, const double *Lm, size_t ld, const double *stag
     d_val2.alloc(nnz);
     d_pos2.alloc(nnz);
     size_t tmp_bytes = 0;
-    MSW_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_val.p, d_val2.p, d_pos.p, d_pos2.p, (size_t)nnz, 0u, 64u, st));
+    MSW_HIP(prim_sort_pairs(nullptr, tmp_bytes, d_val.p, d_val2.p, d_pos.p, d_pos2.p, (size_t)nnz, 64u, st));
     DevBuf<unsigned char> tmp;
     tmp.alloc(tmp_bytes);
-    MSW_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, d_val.p, d_val2.p, d_pos.p, d_pos2.p, (size_t)nnz, 0u, 64u, st));
+    MSW_HIP(prim_sort_pairs(tmp.p, tmp_bytes, d_val.p, d_val2.p, d_pos.p, d_pos2.p, (size_t)nnz, 64u, st));
     d_head.alloc(nnz);
     const unsigned nbn = (unsigned)std::min<uint64_t>((nnz + 255) / 256, (uint64_t)h->n_cu * 32);
     hipLaunchKernelGGL(k_value_heads, dim3(nbn), dim3(256), 0, st, d_val2.p, nnz, d_head.p);

@@ -1,4 +1,4 @@
-// host_em.inc -- EM driver (included by msweep_core.hip).  `prec` (--emprecision, src/mSWEEP.cpp:129,202): double runs
+// host_em.inc -- EM driver (included by solve.hip).  `prec` (--emprecision, src/mSWEEP.cpp:129,202): double runs
 // k_passB + k_em_fin per iteration; float (round 5) runs the fp32 sweeps of em_f32_kernels.hpp where the layout allows
 // (em_f32_layout_ok: offset records with the table in LDS, index records whose float image fits) and the fp64 kernels
 // elsewhere -- msw_timing::em_float_kernels reports which.
@@ -20,8 +20,7 @@ void run_em(const Resident &L, Solver &s, size_t max_iters, int prec) {
   if (f32) {
     s.e32.alloc((size_t)G + kSentinels);
     s.tab32.alloc(std::max<uint32_t>(L.n_area, 1));  // (every entry of the slot area, in its order: lut_area -- a hybrid area's too)
-    hipLaunchKernelGGL(k_em_f32_prep, dim3(1), dim3(1024), 0, s.stream, s.sc.p, G, (int)L.n_area, L.lut_area.p, s.e.p,
-                       s.e32.p, s.tab32.p);
+    em_f32_prep(L, s);  // (k_em_f32_prep: sweep_dense.hip)
   }
   size_t enq = 0;
   while (enq < max_iters) {

@@ -1,4 +1,4 @@
-// host_fastq.inc -- msw_fastq_* (included by msweep_core.hip): --extract-reads, the records of a FASTQ file by read id
+// host_fastq.inc -- msw_fastq_* (included by input.hip): --extract-reads, the records of a FASTQ file by read id
 // (kernels: fastq_kernels.hpp; grammar, messages and the host loops: fastq_host.hpp).  open: the file goes to the device
 // through upload_text (host_reader.inc: plain, gzip and BGZF, the device inflate with zlib behind it), line feeds are
 // counted per tile and scanned, every line's start is written, the records are validated, and the text with
@@ -203,9 +203,9 @@ void fastq_select_impl(msw_core *h, msw_fastq *fq, const uint32_t *ids, size_t n
       fq_alloc(fq->sorted, n, who, "the sorted read ids");
       MSW_HIP(hipMemcpyAsync(fq->ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
       size_t tmp_bytes = 0;
-      MSW_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, fq->ids.p, fq->sorted.p, n, 0u, 32u, st));
+      MSW_HIP(prim_sort_keys(nullptr, tmp_bytes, fq->ids.p, fq->sorted.p, n, 32u, st));
       fq_alloc(fq->tmp, tmp_bytes, who, "sort storage");
-      MSW_HIP(rocprim::radix_sort_keys(fq->tmp.p, tmp_bytes, fq->ids.p, fq->sorted.p, n, 0u, 32u, st));
+      MSW_HIP(prim_sort_keys(fq->tmp.p, tmp_bytes, fq->ids.p, fq->sorted.p, n, 32u, st));
       uint32_t largest = 0;
       MSW_HIP(hipMemcpyAsync(&largest, fq->sorted.p + (n - 1), sizeof largest, hipMemcpyDeviceToHost, st));
       MSW_HIP(hipStreamSynchronize(st));  // (also: `ids` has been read)
@@ -214,20 +214,20 @@ void fastq_select_impl(msw_core *h, msw_fastq *fq, const uint32_t *ids, size_t n
       fq->selected = false;
       fq_alloc(fq->sel, n, who, "the selection");
       fq_alloc(fq->n_sel, 1, who, "the selection's size");
-      MSW_HIP(rocprim::unique(nullptr, tmp_bytes, fq->sorted.p, fq->sel.p, fq->n_sel.p, n, rocprim::equal_to<uint32_t>(), st));
+      MSW_HIP(prim_unique(nullptr, tmp_bytes, fq->sorted.p, fq->sel.p, fq->n_sel.p, n, st));
       fq_alloc(fq->tmp, tmp_bytes, who, "select storage");
-      MSW_HIP(rocprim::unique(fq->tmp.p, tmp_bytes, fq->sorted.p, fq->sel.p, fq->n_sel.p, n, rocprim::equal_to<uint32_t>(), st));
+      MSW_HIP(prim_unique(fq->tmp.p, tmp_bytes, fq->sorted.p, fq->sel.p, fq->n_sel.p, n, st));
       m = fetch_u64(fq->n_sel.p, st);
       if (m > n) throw Fail("msw_fastq_select: internal: more distinct ids than ids");
     }
     fq->selected = false;
     fq_alloc(fq->out_off, m + 1, "msw_fastq_select", "the output offsets");
     if (m) {
-      auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), FqLen{fq->sel.p, fq->rec_off.p, (size_t)m});
+      const FqLen lens{fq->sel.p, fq->rec_off.p, (size_t)m};
       size_t tmp_bytes = 0;
-      MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, lens, fq->out_off.p, (uint64_t)0, (size_t)m + 1, rocprim::plus<uint64_t>(), st));
+      MSW_HIP(prim_scan(nullptr, tmp_bytes, lens, fq->out_off.p, (size_t)m + 1, st));
       fq_alloc(fq->tmp, tmp_bytes, "msw_fastq_select", "scan storage");
-      MSW_HIP(rocprim::exclusive_scan(fq->tmp.p, tmp_bytes, lens, fq->out_off.p, (uint64_t)0, (size_t)m + 1, rocprim::plus<uint64_t>(), st));
+      MSW_HIP(prim_scan(fq->tmp.p, tmp_bytes, lens, fq->out_off.p, (size_t)m + 1, st));
       total = fetch_u64(fq->out_off.p + m, st);
       if (total > fq->n) throw Fail("msw_fastq_select: internal: the selection is longer than the text");
     } else {

@@ -1,4 +1,4 @@
-// host_gzip.inc -- msw_core_gzip_* / msw_core_text_block_gzip (included by msweep_core.hip): --compress z, the gzip
+// host_gzip.inc -- msw_core_gzip_* / msw_core_text_block_gzip (included by output.hip): --compress z, the gzip
 // stream of a text output compressed on the device (deflate_kernels.hpp).  One stream may be open per handle; every call
 // returns the bytes to append to the file in the handle's pinned buffer.  Per call: the text where it lies (a text block:
 // its finished text, text_block_finish of host_text.inc, whose other sink this file is; host bytes: uploaded), the parse
@@ -12,20 +12,30 @@ namespace {
 
 constexpr size_t kGzMaxBytes = (size_t)1 << 30;  // host bytes of one append
 
-void gz_require_open(msw_core *h, const char *who) {
+}  // namespace
+
+// (from here to gz_host_deflate: what msw_fastq_next_gzip of input.hip also calls -- host_api.hpp)
+void msw::host::gz_require_open(msw_core *h, const char *who) {
   if (!h->gz.open) throw Fail(std::string(who) + ": no gzip stream is open on this handle (msw_core_gzip_begin)");
 }
 
-void gz_return(msw_core *h, size_t used, const char **out, size_t *len) {
+void msw::host::gz_return(msw_core *h, size_t used, const char **out, size_t *len) {
   pinned_reserve(h->gz.pinned, 1, 0);  // an empty result still points somewhere
   *out = h->gz.pinned.p;
   *len = used;
   h->gz.bytes_out += used;
 }
 
+// CRC-32 pieces of n bytes of text (k_gz_crc): also what the inflate path of input.hip checks its output with
+void msw::host::gz_crc_launch(int n_cu, hipStream_t st, const uint8_t *text, uint64_t n, const uint32_t *pow8, uint32_t *crc) {
+  const size_t pieces = (size_t)((n + kGzCrcPiece - 1) / kGzCrcPiece);
+  hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((pieces + 255) / 256, (size_t)n_cu * 32))), dim3(256),
+                     0, st, text, n, pow8, crc);
+}
+
 // the chunks of the n bytes of text at d (device memory, 16-byte aligned, readable up to the next multiple of 4)
 // appended to the pinned buffer at `used`; returns the bytes appended
-size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) {
+size_t msw::host::gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) {
   GzState &Z = h->gz;
   if (n == 0) return 0;
   hipStream_t st = h->stream;
@@ -45,9 +55,7 @@ size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) 
   hipLaunchKernelGGL(k_gz_parse, dim3((unsigned)nch), dim3(kWave), 0, st, d, (uint64_t)n, (uint32_t)nch, stored_only ? 1 : 0,
                      Z.tokens.p, Z.tables.p, Z.meta.p, Z.len.p);
   MSW_HIP(hipGetLastError());
-  const size_t pieces = (n + kGzCrcPiece - 1) / kGzCrcPiece;
-  hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((pieces + 255) / 256, (size_t)h->n_cu * 32))),
-                     dim3(256), 0, st, d, (uint64_t)n, Z.pow8.p, Z.crc.p);
+  gz_crc_launch(h->n_cu, st, d, (uint64_t)n, Z.pow8.p, Z.crc.p);
   MSW_HIP(hipGetLastError());
   const uint64_t total = scan_lengths(Z.len.p, Z.off.p, nch, Z.tmp, Z.ev[1], st);
   if (total > n + 10 * nch) throw Fail("msw_core_gzip: the chunks' lengths exceed their stored form");
@@ -73,7 +81,7 @@ size_t gz_compress_device(msw_core *h, const uint8_t *d, size_t n, size_t used) 
 
 // the same for n bytes of pageable host memory: uploaded (16 bytes of slack behind the next multiple of 16), the copy
 // complete before anything that can fail runs
-size_t gz_compress_host(msw_core *h, const char *bytes, size_t n, size_t used) {
+size_t msw::host::gz_compress_host(msw_core *h, const char *bytes, size_t n, size_t used) {
   GzState &Z = h->gz;
   if (n == 0) return 0;
   Z.in.alloc(((n + 15) & ~(size_t)15) + 16);
@@ -83,7 +91,7 @@ size_t gz_compress_host(msw_core *h, const char *bytes, size_t n, size_t used) {
 }
 
 // MSWEEP_HOST_GZIP=1: n bytes of host text through zlib; what it gives out appended at `used`
-size_t gz_host_deflate(msw_core *h, const char *p, size_t n, int flush, size_t used) {
+size_t msw::host::gz_host_deflate(msw_core *h, const char *p, size_t n, int flush, size_t used) {
   GzState &Z = h->gz;
   z_stream &zs = *Z.zs;
   size_t got = 0, left = n;
@@ -104,6 +112,8 @@ size_t gz_host_deflate(msw_core *h, const char *p, size_t n, int flush, size_t u
   Z.isize += n;
   return got;
 }
+
+namespace {
 
 void gz_close(GzState &Z) {
   if (Z.zs) {

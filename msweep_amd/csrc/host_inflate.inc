@@ -1,4 +1,4 @@
-// host_inflate.inc -- gzip pseudoalignment input inflated on the device (included by msweep_core.hip behind
+// host_inflate.inc -- gzip pseudoalignment input inflated on the device (included by input.hip behind
 // host_reader.inc; kernels: inflate_kernels.hpp, format: inflate_format.hpp).  upload_text sends a gzip file's COMPRESSED
 // bytes through the stager and calls inflate_device, which runs the passes on the reader's stream behind the copy's event
 // and leaves the text where the token kernels read it; msw_core_inflate_gzip is the same for bytes in host memory (tests,
@@ -13,15 +13,10 @@
 // member, no probe, windows or chain; the reasons and the host path behind it are the same.
 namespace {
 
-void pinned_reserve(PinnedBuf &B, size_t need, size_t keep);  // host_text.inc
 // files whose first member declares its length (BGZF): host_inflate_members.inc
 bool first_member_declares_length(const uint8_t *head, uint64_t avail);
 int32_t upload_members_device(int fd, const char *path, uint64_t n, ReaderCtx &cx, DevText &t, msw_inflate_info &info);
 int32_t inflate_members_bytes(msw_core *h, const uint8_t *gz, size_t n, const uint8_t **text_out, size_t *len_out, msw_inflate_info &info);
-
-struct OwnerBytes {
-  __host__ __device__ uint64_t operator()(const InfOwner &o) const { return o.bytes; }
-};
 
 bool inflate_forced_to_host() {
   const char *e = getenv("MSWEEP_HOST_INFLATE");
@@ -114,18 +109,16 @@ int32_t inflate_device(ReaderCtx &cx, const uint32_t *d_gz, uint64_t n, const in
   offset.alloc(n_own + 1), crc.alloc(1);
   MSW_HIP(hipMemcpyAsync(owners.p, own.data(), (n_own + 1) * sizeof(InfOwner), hipMemcpyHostToDevice, st));
   {  // (the scan's temporary storage is there before the clock starts)
-    auto it = rocprim::make_transform_iterator(owners.p, OwnerBytes{});
     size_t bytes = 0;
-    MSW_HIP(rocprim::exclusive_scan(nullptr, bytes, it, offset.p, (uint64_t)0, (size_t)n_own + 1, rocprim::plus<uint64_t>(), st));
+    MSW_HIP(prim_scan(nullptr, bytes, owners.p, offset.p, (size_t)n_own + 1, st));
     tmp.alloc(bytes);
   }
   MSW_HIP(hipEventRecord(S.ev[2], st));
   hipLaunchKernelGGL(k_inf_window, dim3(n_own), dim3(kWave), 0, st, d_gz, n_words, end_bit, (uint64_t)1 << 40, n_own, owners.p, windows.p);
   MSW_HIP(hipGetLastError());
   {
-    auto it = rocprim::make_transform_iterator(owners.p, OwnerBytes{});
     size_t bytes = tmp.n;
-    MSW_HIP(rocprim::exclusive_scan(tmp.p, bytes, it, offset.p, (uint64_t)0, (size_t)n_own + 1, rocprim::plus<uint64_t>(), st));
+    MSW_HIP(prim_scan(tmp.p, bytes, owners.p, offset.p, (size_t)n_own + 1, st));  // (the owners' byte counts)
   }
   MSW_HIP(hipEventRecord(S.ev[3], st));
   uint64_t total = 0;
@@ -159,9 +152,7 @@ int32_t inflate_device(ReaderCtx &cx, const uint32_t *d_gz, uint64_t n, const in
   MSW_HIP(hipEventRecord(S.ev[6], st));
   MSW_HIP(hipMemsetAsync(crc.p, 0, sizeof(uint32_t), st));
   if (total) {
-    const size_t pieces = (size_t)((total + kGzCrcPiece - 1) / kGzCrcPiece);
-    hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((pieces + 255) / 256, (size_t)cx.n_cu * 32))), dim3(256),
-                       0, st, txt.p, total, S.pow8.p, crc.p);
+    gz_crc_launch(cx.n_cu, st, txt.p, total, S.pow8.p, crc.p);  // (k_gz_crc: output.hip)
     MSW_HIP(hipGetLastError());
   }
   MSW_HIP(hipEventRecord(S.ev[7], st));

@@ -1,5 +1,5 @@
 // host_inflate_members.inc -- BGZF (bgzip) pseudoalignment input inflated on the device, per member (included by
-// msweep_core.hip behind host_inflate.inc, which calls in here; kernel: inflate_member_kernels.hpp, format and walk:
+// input.hip behind host_inflate.inc, which calls in here; kernel: inflate_member_kernels.hpp, format and walk:
 // inflate_format.hpp).  A gzip file whose first member carries BGZF's 'BC' subfield is walked -- headers and trailers
 // only -- into the table of its members: payload bits, CRC-32, ISIZE and the text offset of each.  The text's length is
 // known from the trailers, so it is allocated once, and one launch decodes every member at its offset and checks it

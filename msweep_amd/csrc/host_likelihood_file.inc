@@ -1,4 +1,4 @@
-// host_likelihood_file.inc -- msw_core_set_dense_logl_file / _text (included by msweep_core.hip behind host_reader.inc;
+// host_likelihood_file.inc -- msw_core_set_dense_logl_file / _text (included by input.hip behind host_reader.inc;
 // kernels: likelihood_text_kernels.hpp).  --read-likelihood (include/Likelihood.hpp:224-253) was the one file-sized stage
 // of the drivers that ran on the host, a float() or std::stod per cell; here the text -- plain, gzip or BGZF, through
 // upload_text -- is parsed where it lies and the resident likelihood is built from the [G][E] stage on, by the code

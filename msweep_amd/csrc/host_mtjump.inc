@@ -1,4 +1,4 @@
-// host_mtjump.inc -- jump-ahead of the MT19937-64 stream (included by msweep_core.hip).
+// host_mtjump.inc -- jump-ahead of the MT19937-64 stream (included by solve.hip).
 // The reference draws all bootstrap replicates from ONE sequential std::mt19937_64
 // (src/BootstrapSample.cpp:60-73), so rank r of a multi-GPU bootstrap starts r * (B / P) * draws
 // words into the stream; stepping there costs 2 ns per word (17 s for the last of 8 ranks at 1000

@@ -1,5 +1,5 @@
 // host_pack.inc -- driver of the device SELL packer (pack_kernels.hpp); included by
-// msweep_core.hip after host_likelihood.inc.
+// build.hip after host_likelihood.inc.
 namespace {
 
 uint64_t device_scan_u32(msw_core *h, uint32_t *d, uint64_t n, DevBuf<uint32_t> &tot, DevBuf<uint64_t> &gt);
@@ -45,8 +45,8 @@ void sell_from_device(msw_core *h, const uint32_t *d_rowptr, const uint32_t *d_g
       const uint64_t nv = std::max<uint64_t>(nnz, 1);
       const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nv + 8191) / 8192, (uint64_t)h->n_cu * 4));
       mm_part.alloc(2 * (size_t)nb);
-      hipLaunchKernelGGL(k_minmax, dim3(nb), dim3(1024), 0, st, nnz ? cell_val : L.lut_area.p, nv, 0, mm_part.p);
-      hipLaunchKernelGGL(k_minmax, dim3(1), dim3(1024), 0, st, mm_part.p, (uint64_t)nb, 1, L.trange.p);
+      minmax_launch(nb, st, nnz ? cell_val : L.lut_area.p, nv, 0, mm_part.p);  // (k_minmax: solve.hip)
+      minmax_launch(1, st, mm_part.p, (uint64_t)nb, 1, L.trange.p);
       MSW_HIP(hipGetLastError());
     }
   } else {
@@ -80,10 +80,10 @@ void sell_from_device(msw_core *h, const uint32_t *d_rowptr, const uint32_t *d_g
   hipLaunchKernelGGL(k_pack_keys, dim3(nbe), dim3(256), 0, st, d_rowptr, E, L.long_row, multilane() ? 1 : 0, d_idx,
                      L.hybrid() ? d_canon.p : (const uint32_t *)nullptr, L.n_tab_lds, key.p, val.p, cnt.p);
   size_t tmp_bytes = 0;
-  MSW_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, L.perm.p, (size_t)E, 0u, kPackKeyBits, st));
+  MSW_HIP(prim_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, L.perm.p, (size_t)E, kPackKeyBits, st));
   DevBuf<unsigned char> tmp;
   tmp.alloc(tmp_bytes);
-  MSW_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, L.perm.p, (size_t)E, 0u, kPackKeyBits, st));
+  MSW_HIP(prim_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, L.perm.p, (size_t)E, kPackKeyBits, st));
   uint32_t counts[1 + kSliceClasses] = {};
   MSW_HIP(hipMemcpyAsync(counts, cnt.p, sizeof counts, hipMemcpyDeviceToHost, st));
   MSW_HIP(hipStreamSynchronize(st));

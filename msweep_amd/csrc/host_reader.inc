@@ -1,4 +1,4 @@
-// host_reader.inc -- the Themisto plaintext reader on the device (included by msweep_core.hip behind
+// host_reader.inc -- the Themisto plaintext reader on the device (included by input.hip behind
 // host_alignment.inc; kernels: reader_kernels.hpp).  Round 5: text -> equivalence classes was 1.5 of the 1.65 s from two
 // strands of 10 M reads to abundances.txt, on 16 host threads; here the text goes to HBM as it is read (pinned staging,
 // two chunks in flight) and every stage of host_alignment.inc -- parse, rows by read id, sorted sets, paired-end merge,
@@ -12,9 +12,6 @@ namespace {
 
 struct ReaderFallback {};  // the text needs the host parser
 
-struct U32ToU64 {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
-};
 // out[i] = in[0] + .. + in[i - 1] for i in [0, n): with in[n - 1] a spare zero, out[n - 1] is the total
 struct ReaderCtx;
 void scan_u32_u64(const uint32_t *in, uint64_t *out, size_t n, ReaderCtx &cx);
@@ -96,11 +93,10 @@ struct DevStrand {
 
 void scan_u32_u64(const uint32_t *in, uint64_t *out, size_t n, ReaderCtx &cx) {
   if (!n) return;
-  auto it = rocprim::make_transform_iterator(in, U32ToU64{});
   size_t bytes = 0;
-  MSW_HIP(rocprim::exclusive_scan(nullptr, bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), cx.st));
+  MSW_HIP(prim_scan(nullptr, bytes, in, out, n, cx.st));
   unsigned char *tmp = cx.scratch(bytes);
-  MSW_HIP(rocprim::exclusive_scan(tmp, bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), cx.st));
+  MSW_HIP(prim_scan(tmp, bytes, in, out, n, cx.st));
 }
 
 // The text of one file in device memory, padded with line feeds to whole tiles (+ one: the parse kernel reads 16 bytes
@@ -296,8 +292,8 @@ void device_strand(DevText &text, size_t n_targets, ReaderCtx &cx, DevStrand &s)
       hipLaunchKernelGGL(k_row_keys, dim3(reader_grid(n_ids, cx.n_cu)), dim3(256), 0, st, s.ptr.p, raw.p, n_ids, flen.p, foff.p,
                          keys.p);
       size_t bytes = 0;
-      MSW_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys.p, keys2.p, (size_t)m, 0u, 64u, st));
-      MSW_HIP(rocprim::radix_sort_keys(cx.scratch(bytes), bytes, keys.p, keys2.p, (size_t)m, 0u, 64u, st));
+      MSW_HIP(prim_sort_keys(nullptr, bytes, keys.p, keys2.p, (size_t)m, 64u, st));
+      MSW_HIP(prim_sort_keys(cx.scratch(bytes), bytes, keys.p, keys2.p, (size_t)m, 64u, st));
       MSW_HIP(hipMemsetAsync(keep.p + m, 0, sizeof(uint32_t), st));
       hipLaunchKernelGGL(k_keys_keep, dim3(reader_grid(m, cx.n_cu)), dim3(256), 0, st, keys2.p, m, keep.p);
       scan_u32_u64(keep.p, kidx.p, m + 1, cx);
@@ -374,8 +370,8 @@ void device_collapse(const DevStrand &s, size_t n_targets, ReaderCtx &cx, msw_al
   MSW_HIP(hipGetLastError());
   if (K) {  // ascending hash; the sort is stable: read ids stay ascending inside a class
     size_t bytes = 0;
-    MSW_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.p, keys2.p, ids.p, out.d_reads.p, (size_t)K, 0u, 64u, st));
-    MSW_HIP(rocprim::radix_sort_pairs(cx.scratch(bytes), bytes, keys.p, keys2.p, ids.p, out.d_reads.p, (size_t)K, 0u, 64u, st));
+    MSW_HIP(prim_sort_pairs(nullptr, bytes, keys.p, keys2.p, ids.p, out.d_reads.p, (size_t)K, 64u, st));
+    MSW_HIP(prim_sort_pairs(cx.scratch(bytes), bytes, keys.p, keys2.p, ids.p, out.d_reads.p, (size_t)K, 64u, st));
   }
   cx.mark("hash + sort");
   head.alloc(K + 1), eidx.alloc(K + 1);

@@ -1,4 +1,4 @@
-// host_text.inc -- msw_core_text_block / msw_core_format_g6 (included by msweep_core.hip): the text of the matrix
+// host_text.inc -- msw_core_text_block / msw_core_format_g6 (included by output.hip): the text of the matrix
 // outputs formatted on the device (text_kernels.hpp).  One pipeline per block of ECs, shared with the gzip stream
 // (host_gzip.inc): materialise the G x w values where they lie (host_likelihood.inc), the length of every line, an
 // exclusive scan, the write pass -- the block's FINISHED text (text_block_finish) -- and a sink: here one copy of the
@@ -17,8 +17,10 @@ uint32_t text_list_cap() {
   return kTextListCap;
 }
 
+}  // namespace
+
 // room for `need` bytes in a pinned buffer, its first `keep` bytes kept
-void pinned_reserve(PinnedBuf &B, size_t need, size_t keep) {
+void msw::host::pinned_reserve(PinnedBuf &B, size_t need, size_t keep) {
   if (need <= B.cap) return;
   const size_t cap = std::max(need, B.cap + B.cap / 2);
   char *p = nullptr;
@@ -32,14 +34,15 @@ void pinned_reserve(PinnedBuf &B, size_t need, size_t keep) {
   B.cap = cap;
 }
 
+namespace {
+
 // off[i] = len[0] + ... + len[i - 1] for i in [0, n], len[n] a spare zero; `scanned` is recorded behind the scan, and
 // off[n], the total, comes back with the stream synchronised
 uint64_t scan_lengths(const uint32_t *len, uint64_t *off, size_t n, DevBuf<uint8_t> &tmp, hipEvent_t scanned, hipStream_t st) {
-  auto len64 = rocprim::make_transform_iterator(len, U32ToU64{});
   size_t tmp_bytes = 0;
-  MSW_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, off, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(prim_scan(nullptr, tmp_bytes, len, off, n + 1, st));
   tmp.alloc(tmp_bytes);
-  MSW_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, len64, off, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), st));
+  MSW_HIP(prim_scan(tmp.p, tmp_bytes, len, off, n + 1, st));
   MSW_HIP(hipEventRecord(scanned, st));
   uint64_t total = 0;
   MSW_HIP(hipMemcpyAsync(&total, off + n, sizeof total, hipMemcpyDeviceToHost, st));

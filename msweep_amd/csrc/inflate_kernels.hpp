@@ -33,14 +33,10 @@
 #pragma once
 #include "common.hpp"
 #include "inflate_format.hpp"
+#include "prim_ops.hpp"  // InfOwner
 
 namespace msw {
 
-struct InfOwner {       // one owner: what the host sets, what pass (a) leaves, what pass (b) adds
-  uint64_t start, stop;  // first bit; the next owner's first bit (infl::kNoStart: to the final block)
-  uint64_t end_bit, bytes;
-  uint32_t status, final, status_b, pad;
-};
 constexpr int kInfChainThreads = 1024;
 static_assert(kWave == 64, "the decode kernels run one wave64 per workgroup in lock step: no barrier orders their LDS traffic");
 

@@ -54,7 +54,7 @@ __device__ inline void prepB_block(Scalars *sc, double a, int G, int n_lut, cons
 // k_prepB (those are then called with n_lut = 0 and this kernel follows them): any number
 // of workgroups, and nothing to do when the tables already belong to the current a (built[0] =
 // version they were built for, built[1] = workgroups that have finished).
-constexpr int kTabInline = 16384;
+// (kTabInline, the size up to which k_finstep / k_prepB rebuild the tables themselves: common.hpp)
 __global__ __launch_bounds__(256) void k_tables(const Scalars *sc, int n_tab, const double *lut, TabDev X,
                                                int *built) {
   const int ver = sc->tab_ver;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(1024) void k_prepB(Scalars *sc, int G, int n_lut, c
 // round trips, not arithmetic: every load is issued up front, BEFORE the state decides what runs; u stays in
 // registers from the step to the exp; one pair of barriers serves the six sums.  Groups beyond kStepRegs * 1024 take
 // the (slower) looping paths.
-constexpr int kStepRegs = 6;  // groups per thread the register paths hold (6144 groups; more: the looping paths)
+// (kStepRegs, the groups per thread the register paths hold: common.hpp)
 __global__ __launch_bounds__(1024) void k_finstep(Scalars *sc, int mode, int G, int n_lut, int n_partA,
                                                  const double *partA, int npartR, const double *totS,
                                                  const double *partR, const double *Nc, const double *w, double *u,

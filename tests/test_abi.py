@@ -73,3 +73,15 @@ def test_library_carries_the_hash_of_its_sources():
     assert core.source_hash() == want
     assert lib.msw_core_version().decode().endswith("src " + want)
     assert g.built_hash(g.LIB) == want
+
+
+def test_crossing_namespace_is_not_exported():
+    """What the translation units of the library call in one another (csrc/host_api.hpp, namespace msw::host, hidden
+    visibility) is no part of the exported surface: no defined dynamic symbol carries that namespace."""
+    import subprocess
+    core.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", core.LIB_PATH], text=True)
+    syms = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
+    assert len(syms) > 50 and "msw_core_create" in syms
+    bad = [s for s in syms if "N3msw4host" in s]      # the Itanium mangling of msw::host::
+    assert not bad, bad[:10]

@@ -3,8 +3,8 @@ instantiation msw_core_bin_reads launches (four record encodings x slot map in L
 pass; the offsets and the scatter), compiled in a translation unit of their own as tests/test_kernel_resources.py does
 for the sweeps."""
 import os
-import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,22 +20,7 @@ P(kEncIndex, true) P(kEncIndex, false) P(kEncValue, true) P(kEncValue, false)
 
 
 def test_bin_kernels_have_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "bin.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "bin.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln)
-        if m and cur:
-            res[cur] = int(m.group(1))
+    res = {k: v["ScratchSize"] for k, v in compile_resources(TU, tmp_path, "bin").items()}
     for frag, n in (("k_bin_count", 8), ("k_bin_write", 8), ("k_bin_ptr", 1), ("k_bin_scatter", 1)):
         hit = {k: v for k, v in res.items() if frag in k}
         assert len(hit) == n, (frag, sorted(res))

@@ -6,7 +6,8 @@ tests/test_text_kernel_resources.py does for the text kernels: the code-length b
 areas that are passed in, and an indexed local array would show up here as scratch."""
 import os
 import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,23 +19,7 @@ KERNELS = ("k_gz_parse", "k_gz_emit", "k_gz_crc")
 
 
 def test_gzip_kernels_have_no_scratch_and_fit_lds(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "gz.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "gz.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur:
-            res[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "gz")
     # every kernel host_gzip.inc launches is one of these
     inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_gzip.inc")).read()
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))

@@ -4,7 +4,8 @@ that crosses a record end in four registers, and an indexed local array would sh
 words of LDS at most.  Compiled in a translation unit of their own, as tests/test_deflate_kernel_resources.py does."""
 import os
 import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -16,23 +17,7 @@ KERNELS = ("k_fq_count", "k_fq_index", "k_fq_validate", "k_fq_gather")
 
 
 def test_fastq_kernels_have_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "fq.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "fq.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur:
-            res[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "fq")
     # every kernel host_fastq.inc launches is one of these
     inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_fastq.inc")).read()
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))

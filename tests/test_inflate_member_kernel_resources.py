@@ -4,7 +4,8 @@ holds so little LDS -- the decode tables, the code lengths and the 8-bit 32 KiB 
 160 KiB.  Compiled in a translation unit of its own, parsed as tests/test_inflate_kernel_resources.py parses."""
 import os
 import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -16,23 +17,7 @@ KERNELS = ("k_infm_decode",)
 
 
 def test_member_kernels_have_no_scratch_and_four_fit_a_cu(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "infm.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "infm.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur:
-            res[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "infm")
     # every kernel host_inflate_members.inc launches is one of these, and it launches them with one wavefront a workgroup
     inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_inflate_members.inc")).read()
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))

@@ -7,8 +7,8 @@ of their time, found in the last profile run).  This test compiles the instantia
 (cfg3 / cfg5: offset records; diverse group sizes: index records; cfg2: value records; the fp32 EM sweep; the dense
 sweeps) in a translation unit of their own and holds every one to zero scratch and to its occupancy class."""
 import os
-import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,25 +36,10 @@ LIMITS = [
 
 
 def test_sweeps_fit_their_registers_without_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "mini.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "mini.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", ln)
-        if m and cur:
-            res.setdefault(cur, {})[m.group(1)[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "mini")
     for frag, vmax in LIMITS:
         hit = [(k, v) for k, v in res.items() if frag in k]
         assert len(hit) == 1, (frag, [k for k in res if "k_pass" in k or "k_em" in k or "k_dense" in k])
         name, v = hit[0]
-        assert v["S"] == 0, f"{frag}: {v['S']} bytes of scratch per lane"
-        assert v["V"] <= vmax, f"{frag}: {v['V']} registers (ceiling {vmax})"
+        assert v["ScratchSize"] == 0, f"{frag}: {v['ScratchSize']} bytes of scratch per lane"
+        assert v["VGPRs"] <= vmax, f"{frag}: {v['VGPRs']} registers (ceiling {vmax})"

@@ -4,8 +4,8 @@ own like tests/test_kernel_resources.py.  The kernel is launched with 1024 threa
 registers -- so 128 registers per lane is the ceiling, and a spill (which no parity test sees) would drain the record
 prefetch in every slice: zero scratch."""
 import os
-import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,28 +21,13 @@ LIMITS = [("k_em_passB_f32_idxILb0E", 128), ("k_em_passB_f32_idxILb1E", 128)]
 
 
 def test_index_float_sweep_fits_its_registers_without_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "mini.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "mini.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur:
-            res.setdefault(cur, {})[m.group(1)[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "mini")
     for frag, vmax in LIMITS:
         hit = [(k, v) for k, v in res.items() if frag in k]
         assert len(hit) == 1, (frag, [k for k in res if "k_em" in k])
         name, v = hit[0]
         print(name, v)
-        assert v["S"] == 0, f"{frag}: {v['S']} bytes of scratch per lane"
-        assert v["V"] <= vmax, f"{frag}: {v['V']} registers (ceiling {vmax})"
-        # the sweeps' LDS image starts at LDS address 0: no static LDS of the kernel's own (msweep_core.hip prepare_sweep)
-        assert v["L"] == 0, f"{frag}: {v['L']} bytes of static LDS"
+        assert v["ScratchSize"] == 0, f"{frag}: {v['ScratchSize']} bytes of scratch per lane"
+        assert v["VGPRs"] <= vmax, f"{frag}: {v['VGPRs']} registers (ceiling {vmax})"
+        # the sweeps' LDS image starts at LDS address 0: no static LDS of the kernel's own (sweep_launch.hpp prepare_sweep)
+        assert v["LDS Size"] == 0, f"{frag}: {v['LDS Size']} bytes of static LDS"

@@ -4,7 +4,8 @@ scratch memory -- the 40 bytes a thread holds and the token's 24 stay in registe
 16 KiB of LDS.  Compiled in a translation unit of its own, parsed as tests/test_inflate_member_kernel_resources.py parses."""
 import os
 import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -16,23 +17,7 @@ KERNELS = ("k_lik_count", "k_lik_parse", "k_lik_scatter", "k_lik_transpose")
 
 
 def test_likelihood_text_kernels_have_no_scratch_and_little_lds(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "liktext.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "liktext.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", ln)
-        if m and cur:
-            res[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+    res = compile_resources(TU, tmp_path, "liktext")
     # every kernel host_likelihood_file.inc launches is among those compiled here
     inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_likelihood_file.inc")).read()
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))

@@ -6,7 +6,8 @@ tests/test_bin_kernel_resources.py does for the bin pass.  The "%g" routine keep
 indexed array of characters or digits would show up here as scratch."""
 import os
 import re
-import subprocess
+
+from kernel_resources import compile_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,25 +22,9 @@ P(kTextProbs) P(kTextLogl) P(kTextBitseq) P(kTextPlain)
 
 
 def test_text_kernels_have_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = tmp_path / "text.hip"
-    src.write_text(TU)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-I", os.path.join(ROOT, "msweep_amd", "csrc"),
-                        "-Rpass-analysis=kernel-resource-usage", str(src), "-o", str(tmp_path / "text.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, lds, cur = {}, {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln)
-        if m and cur:
-            res[cur] = int(m.group(1))
-        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", ln)
-        if m and cur:
-            lds[cur] = int(m.group(1))
+    full = compile_resources(TU, tmp_path, "text")
+    res = {k: v["ScratchSize"] for k, v in full.items()}
+    lds = {k: v["LDS Size"] for k, v in full.items()}
     # every kernel host_text.inc launches is one of these
     inc = open(os.path.join(ROOT, "msweep_amd", "csrc", "host_text.inc")).read()
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", inc))

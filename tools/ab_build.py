@@ -7,18 +7,20 @@ that tools/ab_bench.sh -- or any script through MSWEEP_CORE_LIB -- times in one 
 atomics ...: DESIGN.md 5 quotes their results; the hooks did not survive the round-3 record refactor.)
 usage: ab_build.py name "-DMACRO=value ..." [name flags]..."""
 import os
-import subprocess
 import sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R)
+from msweep_amd import buildlib  # noqa: E402
+
 args = [a for a in sys.argv[1:] if a != "--nopatch"]      # (accepted for old command lines)
 if len(args) < 2 or len(args) % 2:
     sys.exit(__doc__)
-os.makedirs(os.path.join(R, "build_ab"), exist_ok=True)
 for name, flags in zip(args[0::2], args[1::2]):
+    # objects of a variant under build_ab/<name>/: a second build with the same flags recompiles what changed
     out = os.path.join(R, "build_ab", f"lib_{name}.so")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *flags.split(),
-           "-o", out, os.path.join(R, "msweep_amd", "csrc", "msweep_core.hip"), "-L/opt/rocm/lib", "-lrccl", "-lz",
-           "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    print(name, "OK" if r.returncode == 0 else "FAILED\n" + "\n".join(l for l in r.stderr.splitlines() if "error" in l)[:2000])
+    try:
+        took = buildlib.build_library(out, extra_flags=flags.split(), build_dir=os.path.join(R, "build_ab", name))
+        print(name, "OK", " ".join(f"{u}:{s:.0f}s" for u, s in took.items()))
+    except RuntimeError as ex:
+        print(name, "FAILED\n" + "\n".join(l for l in str(ex).splitlines() if "error" in l)[:2000])

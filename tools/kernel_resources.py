@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool: registers / scratch / occupancy of the sweep kernels from
 `hipcc -Rpass-analysis=kernel-resource-usage` output (stderr of a compile saved to a file).
-usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c msweep_core.hip 2> res.txt; kernel_resources.py res.txt [filter]"""
+usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c sweep_narrow.hip 2> res.txt   (any unit of msweep_amd/buildlib.py UNITS, from msweep_amd/csrc); kernel_resources.py res.txt [filter]"""
 import re
 import subprocess
 import sys

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers / scratch / occupancy of a few sweep instantiations compiled ALONE (seconds instead of the library's four minutes).
+# Registers / scratch / occupancy of a few sweep instantiations compiled ALONE (seconds instead of the minutes a sweep unit of the library takes: msweep_amd/buildlib.py).
 # usage: mini_tu.sh "<extra hipcc flags, e.g. -DMSW_PASSB_BATCH=2>"   (edit the instantiation list below as needed)
 set -e
 d=$(mktemp -d)
