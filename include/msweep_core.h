@@ -213,6 +213,51 @@ struct msw_alignment;
 int msw_core_bin_reads_aln(msw_handle h, struct msw_alignment *a, const uint32_t *targets, const double *thresholds,
                            size_t n_targets, uint64_t *bin_ptr, uint32_t *reads_out, double *log_thr_out);
 
+/* What `mGEMS bin` gives beyond the target bins (docs/pipeline.md:54-64), on the device, from the last solve
+ * (msweep_amd/csrc/assign_kernels.hpp; DESIGN.md 7h, [UPSTREAM-UNVERIFIED] like the rule of msw_core_bin_reads): every EC
+ * is judged against ALL estimated groups, pass(g, j) <=> gamma(g, j) >= log(thresholds[g]) with the gamma
+ * msw_core_gamma_block returns and log formed on the host; a NaN compares false.
+ *   thresholds[n_groups]   t_g in [0, 1] for EVERY estimated group (the drivers pass 1 - theta_g)
+ *   targets[n_targets]     rows of the groups whose bins are wanted, each at most once; n_targets == 0 is valid
+ *   flags                  MSW_ASSIGN_UNASSIGNED: bin_ptr has n_targets + 2 entries and bin n_targets holds the reads of
+ *                          the ECs no group claims (n_assigned == 0), ECs in EC order -- reads that did not pseudoalign
+ *                          are in no EC, hence not in it.  MSW_ASSIGN_KEEP_TABLE: the ECs' target lists and an index of
+ *                          the reads by id stay on the handle for msw_core_assign_table_*
+ *   bin_ptr / reads_out    as msw_core_bin_reads; the target bins ARE msw_core_bin_reads' for the same targets and
+ *                          thresholds[targets[k]], id for id
+ *   n_assigned_out[n_ecs]  optional: the groups, of all n_groups, that claim each EC
+ *   class_reads_out[3]     optional: the reads in ECs claimed by 0, by 1 and by >= 2 groups
+ * Device memory O(E + pairs + aligned reads + output); an allocation that fails is an error naming the bytes.  No atomic
+ * decides an order: two calls give the same bytes.  Every call runs the whole pass.
+ * Refused like msw_core_bin_reads (no solve yet, n_ecs != E, a target out of range or repeated, the dense flavour, a
+ * communicator set), and for a threshold of ANY group that is NaN or outside [0, 1]. */
+#define MSW_ASSIGN_UNASSIGNED 1u /* bin_ptr has n_targets + 2 entries; bin n_targets = the unassigned reads */
+#define MSW_ASSIGN_KEEP_TABLE 2u /* keep the per-class target lists and the reads-by-id index on the handle */
+int msw_core_assign_reads(msw_handle h, const uint64_t *ec_rptr, const uint32_t *ec_reads, size_t n_ecs,
+                          const double *thresholds, const uint32_t *targets, size_t n_targets, unsigned flags,
+                          uint64_t *bin_ptr, uint32_t *reads_out, uint32_t *n_assigned_out, uint64_t class_reads_out[3]);
+/* The same on an alignment handle (as msw_core_bin_reads_aln). */
+int msw_core_assign_reads_aln(msw_handle h, struct msw_alignment *a, const double *thresholds, const uint32_t *targets,
+                              size_t n_targets, unsigned flags, uint64_t *bin_ptr, uint32_t *reads_out,
+                              uint32_t *n_assigned_out, uint64_t class_reads_out[3]);
+/* The read x target assignment table of the last msw_core_assign_reads[_aln] call with MSW_ASSIGN_KEEP_TABLE, as text
+ * formatted on the device: one row per aligned read in ascending read id -- the (read id, EC) pairs in a stable sort by
+ * id, so an id that host-supplied arrays list in two ECs gives two rows --, dec(id), then per target in target order
+ * "\t1" if the read's EC passes it, else "\t0", then '\n'.  With n_targets == 0 the rows are bare ids.
+ *   msw_core_assign_table_rows        the number of rows (the aligned reads)
+ *   msw_core_assign_table_block       the rows [row_begin, row_end) in the handle's pinned text buffer (valid until the
+ *                                     next text or table call)
+ *   msw_core_assign_table_block_gzip  the same rows into the open gzip stream (msw_core_gzip_begin): the bytes to append
+ *                                     to the file; text_len_out: their uncompressed length
+ * The kept state is dropped by a new resident likelihood (set_*, build_*), a solve, a bootstrap, and an assign call
+ * without MSW_ASSIGN_KEEP_TABLE.  Refused: no kept state, a row range out of bounds, a block whose worst-case text
+ * (11 + 2 n_targets bytes per row) exceeds 1 GiB -- the message says how many rows fit --, the gzip variant without an
+ * open stream. */
+int msw_core_assign_table_rows(msw_handle h, size_t *n_rows_out);
+int msw_core_assign_table_block(msw_handle h, size_t row_begin, size_t row_end, const char **text_out, size_t *len_out);
+int msw_core_assign_table_block_gzip(msw_handle h, size_t row_begin, size_t row_end, const char **out, size_t *len_out,
+                                     size_t *text_len_out);
+
 /* The text of the matrix outputs, formatted on the device (text_kernels.hpp): the lines of the ECs [ec_begin, ec_end)
  * as contiguous bytes in EC order, every cell printed as the reference's default `ostream <<` prints a double --
  * printf("%g"), byte for byte (g6_format.hpp).  Only the bytes cross the link; nothing is sized G x E.

@@ -8,6 +8,9 @@ gzip stream compressed on the device as well (Core.gzip_begin / text_block_gzip 
 and zstd are refused, and --compression-level 1 ... 9 all run the core's one parse (0 stores).
 --extract-reads A[,B,...] goes one step further than the bins: `<dir>/<group>_<k>.fastq` holds the binned reads of the k-th
 FASTQ file themselves, gathered on the device where the file lies (Core.fastq_open; extract_reads below).
+--write-unassigned / --write-assignment-table (with --bin-reads) add what `mGEMS bin` gives beyond the target bins:
+`<dir>/unassigned_reads.bin`, the aligned reads no estimated group claims, and `<prefix>_reads_to_groups.tsv`, a 0/1 column
+per target for every aligned read, formatted on the device (Core.assign_reads_aln / assign_table_block).
 Every tab-separated column of the -i file is a grouping of its own: the estimation runs once per column
 (src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several."""
 import argparse
@@ -57,6 +60,10 @@ def parse(argv):
     ap.add_argument("--min-abundance", type=float)
     ap.add_argument("--extract-reads", type=lambda v: v.split(","),
                     help="FASTQ files A[,B,...] (plain, gzip or BGZF): with --bin-reads, <group>_<k>.fastq per target group and file")
+    ap.add_argument("--write-unassigned", action="store_true",
+                    help="with --bin-reads: <dir>/unassigned_reads.bin, the aligned reads no estimated group claims")
+    ap.add_argument("--write-assignment-table", action="store_true",
+                    help="with --bin-reads: <prefix>_reads_to_groups.tsv, a 0/1 column per target group for every aligned read")
     ap.add_argument("--compress", default="plaintext", help="plaintext or z (gzip, written on the device)")
     ap.add_argument("--compression-level", type=int, default=6, help="0 stores; 1 ... 9 run the same parse")
     ap.add_argument("--device", type=int, default=0)
@@ -106,6 +113,9 @@ class GzipOut:
 
     def text_block(self, what, e0, e1, **kw):
         self.f.write(self.core.text_block_gzip(what, e0, e1, **kw))
+
+    def table_block(self, r0, r1):
+        self.f.write(self.core.assign_table_block_gzip(r0, r1))
 
     def pieces(self, pieces):
         """bytes the stream has given out already (Fastq.pieces_gzip)"""
@@ -296,20 +306,49 @@ def extract_reads(core, aln, targets, bin_ptr, reads, a):
     return 0
 
 
-def bin_reads(core, aln, estimated_names, theta, a):
+def write_assignment_table(core, path, targets, a):
+    """--write-assignment-table: `#read_id` and the target names, then the rows of the table the device kept
+    (Core.assign_table_block), a block of binning.table_block_rows at a time: only bytes come to the host."""
+    with _open_out(core, path, a) as f:
+        f.write(binning.table_header(targets))
+        n, block = core.assign_table_rows(), binning.table_block_rows(len(targets))
+        for r0 in range(0, n, block):
+            r1 = min(n, r0 + block)
+            if isinstance(f, GzipOut):
+                f.table_block(r0, r1)
+            else:
+                f.write(core.assign_table_block(r0, r1))
+
+
+def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
     """--bin-reads (src/mSWEEP.cpp:437-469): targets, thresholds 1 - theta, the bins from the device, one file per
-    target (an empty bin gives an empty file), then --extract-reads.  Returns the exit status."""
+    target (an empty bin gives an empty file), then --extract-reads.  With --write-unassigned / --write-assignment-table
+    the bins come from Core.assign_reads_aln, which judges every class against all estimated groups: one more bin for the
+    reads nobody claims, and the table.  Returns the exit status."""
+    extras = a.write_unassigned or a.write_assignment_table
     try:
         targets = binning.resolve_targets(estimated_names, a.target_groups)
         if a.min_abundance is not None:
             targets = binning.filter_min_abundance(targets, estimated_names, theta, a.min_abundance)
         row = {n: i for i, n in enumerate(estimated_names)}
         rows = [row[t] for t in targets]
-        bin_ptr, reads, _ = core.bin_reads_aln(aln, rows, binning.thresholds(rows, theta))
+        if extras:
+            if a.write_unassigned:
+                binning.check_unassigned_name(estimated_names)
+            res = core.assign_reads_aln(aln, binning.all_thresholds(theta), rows, unassigned=a.write_unassigned,
+                                        keep_table=a.write_assignment_table)
+            bin_ptr, reads = res["bin_ptr"], res["reads"]
+            if a.verbose:
+                c0, c1, c2 = (int(x) for x in res["class_reads"])
+                sys.stderr.write(f"note: {note}reads assigned to one group: {c1}, to several: {c2}, to none: {c0}, "
+                                 f"of {c0 + c1 + c2} aligned reads\n")
+        else:
+            bin_ptr, reads, _ = core.bin_reads_aln(aln, rows, binning.thresholds(rows, theta))
     except (binning.BinningError, MswError) as ex:
         sys.stderr.write(f"Binning the reads failed:\n  {ex}\nexiting\n")
         return 1
-    for k, name in enumerate(targets):
+    bins = list(targets) + ([binning.UNASSIGNED] if a.write_unassigned else [])    # the unassigned bin is the last one
+    for k, name in enumerate(bins):
         try:
             ids = reads[int(bin_ptr[k]):int(bin_ptr[k + 1])]
             if a.compress == "z":
@@ -320,8 +359,14 @@ def bin_reads(core, aln, estimated_names, theta, a):
         except (OSError, MswError) as ex:
             sys.stderr.write(f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
             return 1
+    if a.write_assignment_table:
+        try:
+            write_assignment_table(core, table_path, targets, a)
+        except (OSError, MswError) as ex:
+            sys.stderr.write(f"Writing the assignment table failed:\n  {ex}\nexiting\n")
+            return 1
     if a.extract_reads:
-        return extract_reads(core, aln, targets, bin_ptr, reads, a)
+        return extract_reads(core, aln, bins, bin_ptr, reads, a)
     return 0
 
 
@@ -343,6 +388,10 @@ def main(argv=None):
         # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
         sys.stderr.write("Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n")
         return 1
+    for flag, on in (("--write-unassigned", a.write_unassigned), ("--write-assignment-table", a.write_assignment_table)):
+        if on and not a.bin_reads:
+            sys.stderr.write(f"Binning the reads failed:\n  {flag} needs --bin-reads\nexiting\n")
+            return 1
     if a.extract_reads is not None:
         # --extract-reads: the bins are its input, and every path names a file
         if not a.bin_reads:
@@ -495,7 +544,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
     if a.bin_reads:
         # before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
         est = [n for n, m in zip(grouping.get_names(), lik.groups_considered()) if m]
-        rc = bin_reads(core, aln, est, res["theta"], a)
+        rc = bin_reads(core, aln, est, res["theta"], a, path("reads_to_groups.tsv"), note)
         if rc:
             return rc
     try:

@@ -2,6 +2,8 @@
 device (Core.bin_reads_aln: msweep_amd/csrc/bin_kernels.hpp); this module holds, one function each, what the drivers
 decide around them: which groups are targets, the --min-abundance filter, the thresholds 1 - theta, where a bin is
 written and how.  The native driver (msweep_amd/cpp/msweep_mini.cpp) makes the same choices and writes the same bytes.
+--write-unassigned / --write-assignment-table (Core.assign_reads_aln: msweep_amd/csrc/assign_kernels.hpp)
+add the file of the unassigned bin, the table's header and its rows per block.
 
 mGEMS itself is not vendored by the reference (fetched at configure time), so the rule is restated from the mGEMS paper
 (Maklin et al., Microbial Genomics 7:11, 2021); DESIGN.md marks it [UPSTREAM-UNVERIFIED]."""
@@ -51,6 +53,36 @@ def extract_path(prefix, name, k):
     """--extract-reads: the reads of target group `name` from the k-th FASTQ file (k from 1), beside the bins:
     <dir>/<name>_<k>.fastq.  This project's own rule [UPSTREAM-UNVERIFIED]: mGEMS is not vendored by the reference."""
     return bin_path(prefix, name)[:-len(".bin")] + f"_{k}.fastq"
+
+
+UNASSIGNED = "unassigned_reads"      # --write-unassigned: the bin of the reads no estimated group claims
+
+
+def unassigned_path(prefix):
+    """--write-unassigned: <dir>/unassigned_reads.bin, beside the bins (bin_path)."""
+    return bin_path(prefix, UNASSIGNED)
+
+
+def check_unassigned_name(estimated_names):
+    """An estimated group literally named `unassigned_reads` would share the file of the unassigned bin: refused."""
+    if UNASSIGNED in estimated_names:
+        raise BinningError(f"a group is named {UNASSIGNED}, the name of the file --write-unassigned writes")
+
+
+def all_thresholds(abundances):
+    """t_g = 1 - theta_g for EVERY estimated group: what Core.assign_reads_aln judges every class against."""
+    return 1.0 - np.asarray(abundances, np.float64)
+
+
+def table_header(target_names):
+    """first line of <prefix>_reads_to_groups.tsv: `#read_id`, then the target names in target order"""
+    return ("\t".join(["#read_id"] + list(target_names)) + "\n").encode()
+
+
+def table_block_rows(n_targets):
+    """Rows per Core.assign_table_block call: 2^20, fewer when the worst-case text of a block (11 + 2 n_targets bytes per
+    row) would exceed 256 MiB."""
+    return max(1, min(1 << 20, (256 << 20) // (11 + 2 * int(n_targets))))
 
 
 def format_ids(ids):

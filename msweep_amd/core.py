@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MSWEEP_CORE_LIB") or os.path.join(_HERE, "libmsweep_c
 ALGO_RCG, ALGO_EM = 0, 1
 PREC_DOUBLE, PREC_FLOAT = 0, 1
 TEXT_PROBS, TEXT_LOGL, TEXT_BITSEQ = 0, 1, 2      # msw_core_text_block
+ASSIGN_UNASSIGNED, ASSIGN_KEEP_TABLE = 1, 2       # msw_core_assign_reads flags
 # msw_core_set_option ids (include/msweep_core.h): the knobs of rcgpar's loops that are restated from memory
 OPT_CHECK_EVERY, OPT_INIT_BOUND, OPT_EM_PRIOR, OPT_EM_STOP = 0, 1, 2, 3
 _OPTS = {"check_every": OPT_CHECK_EVERY, "init_bound": OPT_INIT_BOUND, "em_prior": OPT_EM_PRIOR, "em_stop": OPT_EM_STOP}
@@ -37,6 +38,8 @@ EXPORTS = [
     "msw_comm_size", "msw_comm_rccl_count", "msw_comm_allgather", "msw_comm_allreduce", "msw_comm_create_shm", "msw_core_continue", "msw_core_gamma_block",
     "msw_core_last_bootstrap_timing", "msw_core_layout_info", "msw_core_guarded_visits", "msw_core_set_pack_schedule",
     "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
+    "msw_core_assign_reads", "msw_core_assign_reads_aln", "msw_core_assign_table_rows", "msw_core_assign_table_block",
+    "msw_core_assign_table_block_gzip",
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
     "msw_core_inflate_gzip", "msw_alignment_last_inflate",
@@ -174,6 +177,12 @@ def load_library():
     L.msw_core_gamma_block.argtypes = [vp, sz, sz, vp, sz]
     L.msw_core_bin_reads.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
     L.msw_core_bin_reads_aln.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp]
+    if hasattr(L, "msw_core_assign_reads"):     # (a library of an earlier commit behind MSWEEP_CORE_LIB has none of them)
+        L.msw_core_assign_reads.argtypes = [vp, vp, vp, sz, vp, vp, sz, C.c_uint, vp, vp, vp, vp]
+        L.msw_core_assign_reads_aln.argtypes = [vp, vp, vp, vp, sz, C.c_uint, vp, vp, vp, vp]
+        L.msw_core_assign_table_rows.argtypes = [vp, C.POINTER(sz)]
+        L.msw_core_assign_table_block.argtypes = [vp, sz, sz, C.POINTER(vp), C.POINTER(sz)]
+        L.msw_core_assign_table_block_gzip.argtypes = [vp, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.msw_core_text_block.argtypes = [vp, C.c_int, sz, sz, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.msw_core_format_g6.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.msw_core_last_text_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64)]
@@ -747,6 +756,69 @@ class Core:
         reads = np.empty(int(bin_ptr[-1]), np.uint32)
         self._check(call(_ptr(targets), _ptr(thresholds), n, _ptr(bin_ptr), _ptr(reads), None))
         return bin_ptr, reads, log_thr
+
+    def assign_reads(self, ec_rptr, ec_reads, thresholds, targets, unassigned=True, keep_table=False, want_reads=True):
+        """Every EC judged against ALL estimated groups (msw_core_assign_reads): pass(g, j) <=> gamma(g, j) >=
+        log(thresholds[g]), thresholds for every group.  Returns a dict: bin_ptr (n_targets + 1 entries, one more with
+        `unassigned`, whose last bin holds the reads no group claims), reads (or None), n_assigned[E] (groups that claim
+        each EC) and class_reads (reads in ECs claimed by 0 / 1 / >= 2 groups).  keep_table: assign_table_* serve the
+        read x target table of this call."""
+        ec_rptr = _arr(ec_rptr, np.uint64)
+        ec_reads = _arr(ec_reads, np.uint32)
+        if len(ec_rptr) == 0 or int(ec_rptr[-1]) > len(ec_reads):
+            raise MswError("assign_reads: ec_rptr does not describe ec_reads")
+        return self._assign(lambda th, t, n, fl, bp, out, na, cl: self._L.msw_core_assign_reads(
+            self._h, _ptr(ec_rptr), _ptr(ec_reads), len(ec_rptr) - 1, th, t, n, fl, bp, out, na, cl),
+            len(ec_rptr) - 1, thresholds, targets, unassigned, keep_table, want_reads)
+
+    def assign_reads_aln(self, aln, thresholds, targets, unassigned=True, keep_table=False, want_reads=True):
+        """assign_reads on the classes of an alignment (msw_core_assign_reads_aln): a DeviceAlignment on this GPU is read
+        where it lies."""
+        return self._assign(lambda th, t, n, fl, bp, out, na, cl: self._L.msw_core_assign_reads_aln(
+            self._h, aln._h, th, t, n, fl, bp, out, na, cl), int(aln.n_ecs), thresholds, targets, unassigned, keep_table,
+            want_reads)
+
+    def _assign(self, call, n_ecs, thresholds, targets, unassigned, keep_table, want_reads):
+        thresholds = _arr(thresholds, np.float64)
+        targets = _arr(targets, np.uint32)
+        if thresholds.ndim != 1 or targets.ndim != 1:
+            raise MswError("assign_reads: thresholds and targets must be 1-D arrays")
+        if self.shape()[0] != len(thresholds):
+            raise MswError("assign_reads: one threshold per estimated group")
+        n = len(targets)
+        flags = (ASSIGN_UNASSIGNED if unassigned else 0) | (ASSIGN_KEEP_TABLE if keep_table else 0)
+        bin_ptr = np.zeros(n + 1 + (1 if unassigned else 0), np.uint64)
+        n_assigned = np.zeros(max(int(n_ecs), 0), np.uint32)
+        cls = np.zeros(3, np.uint64)
+        reads = None
+        if want_reads:      # the sizes first, then the fill: every call runs the whole pass
+            self._check(call(_ptr(thresholds), _ptr(targets), n, flags & ~ASSIGN_KEEP_TABLE, _ptr(bin_ptr), None, None, None))
+            reads = np.empty(int(bin_ptr[-1]), np.uint32)
+        self._check(call(_ptr(thresholds), _ptr(targets), n, flags, _ptr(bin_ptr), _ptr(reads) if want_reads else None,
+                         _ptr(n_assigned), _ptr(cls)))
+        return dict(bin_ptr=bin_ptr, reads=reads, n_assigned=n_assigned, class_reads=cls)
+
+    def assign_table_rows(self):
+        """rows of the kept assignment table: the aligned reads (msw_core_assign_table_rows)"""
+        n = C.c_size_t()
+        self._check(self._L.msw_core_assign_table_rows(self._h, C.byref(n)))
+        return n.value
+
+    def assign_table_block(self, row_begin, row_end):
+        """The rows [row_begin, row_end) of the kept assignment table as text formatted on the device
+        (msw_core_assign_table_block): "id\t0\t1...\n" per aligned read, ascending id.  A copy of the bytes."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.msw_core_assign_table_block(self._h, int(row_begin), int(row_end), C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def assign_table_block_gzip(self, row_begin, row_end, with_info=False):
+        """assign_table_block into the open gzip stream (msw_core_assign_table_block_gzip): the compressed bytes and,
+        with_info, the uncompressed length."""
+        p, n, nt = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._check(self._L.msw_core_assign_table_block_gzip(self._h, int(row_begin), int(row_end), C.byref(p), C.byref(n),
+                                                             C.byref(nt)))
+        out = C.string_at(p.value, n.value) if n.value else b""
+        return (out, nt.value) if with_info else out
 
     def set_trace_theta(self, n):
         self._check(self._L.msw_core_set_trace_theta(self._h, int(n)))

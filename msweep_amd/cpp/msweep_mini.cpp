@@ -15,6 +15,9 @@
 // the Python mirror `python -m msweep_amd` in tests/test_gpu_cli_toy.py.
 // --extract-reads A[,B,...] (with --bin-reads): `<dir>/<group>_<k>.fastq[.gz]`, the binned reads of the k-th FASTQ file
 // themselves, gathered on the device where the file lies (msw_fastq_*; the step docs/pipeline.md:59-64 gives to mGEMS).
+// --write-unassigned / --write-assignment-table (with --bin-reads): `<dir>/unassigned_reads.bin`, the aligned reads no
+// estimated group claims, and `<prefix>_reads_to_groups.tsv`, a 0/1 column per target for every aligned read, formatted on
+// the device (msw_core_assign_reads_aln, msw_core_assign_table_block).
 // Every tab-separated column of the -i file is a grouping of its own and the whole estimation runs once per column
 // (src/mSWEEP.cpp:282) -- from ONE read of the pseudoalignment, whose classes stay in device memory: run_grouping() is the
 // body of that loop, out_path() names its files (`<prefix>_<i>_...` when there are several; tests/test_gpu_groupings.py).
@@ -58,6 +61,7 @@ struct Args {
   bool bin_reads = false, have_target_groups = false, have_min_abundance = false;
   std::vector<std::string> target_groups;
   double min_abundance = 0.0;
+  bool write_unassigned = false, write_assignment_table = false;  // with --bin-reads: the unassigned bin, the table
   bool have_extract_reads = false;
   std::vector<std::string> extract_reads;  // --extract-reads A[,B,...]: the FASTQ files the bins are extracted from
   std::string compress = "plaintext";  // or "z"
@@ -110,6 +114,8 @@ Args parse(int argc, char **argv) {
     else if (k == "--no-fit-model") a.no_fit_model = true;
     else if (k == "--run-rate") a.run_rate = true;
     else if (k == "--bin-reads") a.bin_reads = true;
+    else if (k == "--write-unassigned") a.write_unassigned = true;
+    else if (k == "--write-assignment-table") a.write_assignment_table = true;
     else if (k == "--compress") a.compress = val();
     else if (k == "--compression-level") a.compression_level = std::stoi(val());
     else if (k == "--target-groups") {
@@ -254,6 +260,14 @@ class Out {
     size_t n = 0;
     if (gz_) check(h_, msw_core_text_block_gzip(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr, nullptr));
     else check(h_, msw_core_text_block(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr));
+    os_->write(p, (std::streamsize)n);
+  }
+  // rows of the assignment table the handle keeps (msw_core_assign_table_block / _gzip)
+  void table_block(size_t r0, size_t r1) {
+    const char *p = nullptr;
+    size_t n = 0;
+    if (gz_) check(h_, msw_core_assign_table_block_gzip(h_, r0, r1, &p, &n, nullptr));
+    else check(h_, msw_core_assign_table_block(h_, r0, r1, &p, &n));
     os_->write(p, (std::streamsize)n);
   }
   bool good() const { return (bool)*os_; }
@@ -460,21 +474,60 @@ int extract_after_bins(const Args &a, msw_handle h, const Run &r, const std::vec
   return extract_reads(a, h, r.n_reads, r.fastqs, r.fastq_records, names, bin_ptr, reads);
 }
 
+// --write-assignment-table: `#read_id` and the target names, then the rows of the table the device kept, a block of
+// table_block_rows at a time (msweep_amd/binning.py: the same header, the same blocks)
+void write_assignment_table(const Args &a, msw_handle h, const std::string &path, const std::vector<std::string> &targets) {
+  Out f(h, path, a.compress == "z", a.compression_level);
+  std::string head = "#read_id";
+  for (const std::string &n : targets) head += "\t" + n;
+  head += "\n";
+  f.write(head);
+  size_t n = 0;
+  check(h, msw_core_assign_table_rows(h, &n));
+  const size_t block = std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, ((size_t)256 << 20) / (11 + 2 * targets.size())));
+  for (size_t r0 = 0; r0 < n; r0 += block) f.table_block(r0, std::min(n, r0 + block));
+  f.close();
+  if (!f.good()) throw std::runtime_error("cannot write " + path);
+}
+
 // the bins from the device and one file per target (an empty bin: an empty file), written on up to writer_threads()
-// threads, then --extract-reads; returns the exit status
+// threads, then --extract-reads; with --write-unassigned / --write-assignment-table the bins come from
+// msw_core_assign_reads_aln, which judges every class against all estimated groups: one more bin, <dir>/unassigned_reads.bin,
+// and the table.  Returns the exit status.
 int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vector<std::string> &est,
-              const std::vector<double> &theta, const Run &r) {
-  std::vector<std::string> names;
+              const std::vector<double> &theta, const Run &r, const std::string &table_path, const std::string &note) {
+  std::vector<std::string> names, targets;
   std::vector<uint64_t> bin_ptr;
   std::vector<uint32_t> reads;
+  const bool extras = a.write_unassigned || a.write_assignment_table;
   try {
     const std::vector<uint32_t> rows = bin_targets(a, est, theta, names);
-    std::vector<double> thr(rows.size());
-    for (size_t k = 0; k < rows.size(); ++k) thr[k] = 1.0 - theta[rows[k]];
-    bin_ptr.assign(rows.size() + 1, 0);
-    check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), nullptr, nullptr));
-    reads.resize(bin_ptr.back());
-    check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), reads.data(), nullptr));
+    targets = names;
+    if (extras) {
+      if (a.write_unassigned && std::find(est.begin(), est.end(), "unassigned_reads") != est.end())
+        throw BinningError("a group is named unassigned_reads, the name of the file --write-unassigned writes");
+      std::vector<double> thr(theta.size());
+      for (size_t g = 0; g < theta.size(); ++g) thr[g] = 1.0 - theta[g];
+      const unsigned unas = a.write_unassigned ? MSW_ASSIGN_UNASSIGNED : 0u;
+      bin_ptr.assign(rows.size() + 1 + (a.write_unassigned ? 1 : 0), 0);
+      uint64_t cls[3] = {0, 0, 0};
+      check(h, msw_core_assign_reads_aln(h, aln, thr.data(), rows.data(), rows.size(), unas, bin_ptr.data(), nullptr, nullptr, nullptr));
+      reads.resize(bin_ptr.back());
+      check(h, msw_core_assign_reads_aln(h, aln, thr.data(), rows.data(), rows.size(),
+                                         unas | (a.write_assignment_table ? MSW_ASSIGN_KEEP_TABLE : 0u), bin_ptr.data(), reads.data(),
+                                         nullptr, cls));
+      if (a.write_unassigned) names.push_back("unassigned_reads");  // the unassigned bin is the last one
+      if (a.verbose)
+        std::cerr << "note: " << note << "reads assigned to one group: " << cls[1] << ", to several: " << cls[2]
+                  << ", to none: " << cls[0] << ", of " << cls[0] + cls[1] + cls[2] << " aligned reads\n";
+    } else {
+      std::vector<double> thr(rows.size());
+      for (size_t k = 0; k < rows.size(); ++k) thr[k] = 1.0 - theta[rows[k]];
+      bin_ptr.assign(rows.size() + 1, 0);
+      check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), nullptr, nullptr));
+      reads.resize(bin_ptr.back());
+      check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), reads.data(), nullptr));
+    }
   } catch (const std::exception &ex) {
     std::cerr << "Binning the reads failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
@@ -500,20 +553,28 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
         return 1;
       }
     }
-    return extract_after_bins(a, h, r, names, bin_ptr, reads);
+  } else {
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < nt; ++t)
+      pool.emplace_back([&, t] {
+        for (size_t k = t; k < n; k += nt)
+          err[k] = write_bin(bin_path(a.prefix, names[k]), reads.data() + bin_ptr[k], bin_ptr[k + 1] - bin_ptr[k]);
+      });
+    for (auto &th : pool) th.join();
+    for (size_t k = 0; k < n; ++k)
+      if (!err[k].empty()) {
+        std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
+        return 1;
+      }
   }
-  std::vector<std::thread> pool;
-  for (size_t t = 0; t < nt; ++t)
-    pool.emplace_back([&, t] {
-      for (size_t k = t; k < n; k += nt)
-        err[k] = write_bin(bin_path(a.prefix, names[k]), reads.data() + bin_ptr[k], bin_ptr[k + 1] - bin_ptr[k]);
-    });
-  for (auto &th : pool) th.join();
-  for (size_t k = 0; k < n; ++k)
-    if (!err[k].empty()) {
-      std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
+  if (a.write_assignment_table) {
+    try {
+      write_assignment_table(a, h, table_path, targets);
+    } catch (const std::exception &ex) {
+      std::cerr << "Writing the assignment table failed:\n  " << ex.what() << "\nexiting\n";
       return 1;
     }
+  }
   return extract_after_bins(a, h, r, names, bin_ptr, reads);
 }
 
@@ -784,7 +845,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
     results.push_back(theta);
     if (a.bin_reads) {
       // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
-      if (bin_reads(a, h, r.aln, est_names, theta, r) != 0) return 1;
+      if (bin_reads(a, h, r.aln, est_names, theta, r, out_path(a.prefix, index, K, "reads_to_groups.tsv"), note) != 0) return 1;
     }
     if (a.iters > 0) {
       // every grouping's bootstrap starts the stream from the same seed (the reference constructs the sample inside its
@@ -888,6 +949,12 @@ int main(int argc, char **argv) {
   if (a.bin_reads && !a.read_likelihood.empty()) {
     // "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
     std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
+    return 1;
+  }
+  if ((a.write_unassigned || a.write_assignment_table) && !a.bin_reads) {
+    // both go with the bins (--write-unassigned is named first when both are given)
+    std::cerr << "Binning the reads failed:\n  " << (a.write_unassigned ? "--write-unassigned" : "--write-assignment-table")
+              << " needs --bin-reads\nexiting\n";
     return 1;
   }
   if (a.have_extract_reads) {

@@ -1,5 +1,6 @@
 // build.hip -- translation unit of the likelihood build: layout planning, upload and packing, the device build, the dense
-// re-expression, gamma and the bin pass (bin_kernels.hpp builds on gamma_kernels.hpp), with their C ABI entries.
+// re-expression, gamma, the bin pass (bin_kernels.hpp builds on gamma_kernels.hpp) and the assign pass with its table
+// (assign_kernels.hpp builds on bin_kernels.hpp), with their C ABI entries.
 #include "host_api.hpp"
 
 #include "sweep_kernels.hpp"
@@ -8,6 +9,7 @@
 #include "compress_kernels.hpp"
 #include "gamma_kernels.hpp"
 #include "bin_kernels.hpp"
+#include "assign_kernels.hpp"
 
 MSW_UNIT_WARM(build)
 
@@ -17,6 +19,7 @@ MSW_UNIT_WARM(build)
 #include "host_build.inc"
 #include "host_compress.inc"
 #include "host_bin.inc"
+#include "host_assign.inc"
 
 extern "C" {
 
@@ -142,6 +145,40 @@ int msw_core_bin_reads_aln(msw_handle h, msw_alignment_t a, const uint32_t *targ
                      targets, thresholds, n_targets, bin_ptr, reads_out, log_thr_out);
     }
   });
+}
+
+int msw_core_assign_reads(msw_handle h, const uint64_t *ec_rptr, const uint32_t *ec_reads, size_t n_ecs, const double *thresholds,
+                          const uint32_t *targets, size_t n_targets, unsigned flags, uint64_t *bin_ptr, uint32_t *reads_out,
+                          uint32_t *n_assigned_out, uint64_t class_reads_out[3]) {
+  return guarded(h, [&] {
+    assign_reads_impl(h, ec_rptr, ec_reads, n_ecs, false, thresholds, targets, n_targets, flags, bin_ptr, reads_out,
+                      n_assigned_out, class_reads_out);
+  });
+}
+
+int msw_core_assign_reads_aln(msw_handle h, msw_alignment_t a, const double *thresholds, const uint32_t *targets, size_t n_targets,
+                              unsigned flags, uint64_t *bin_ptr, uint32_t *reads_out, uint32_t *n_assigned_out,
+                              uint64_t class_reads_out[3]) {
+  return guarded(h, [&] {
+    assign_reads_aln_impl(h, a, thresholds, targets, n_targets, flags, bin_ptr, reads_out, n_assigned_out, class_reads_out);
+  });
+}
+
+int msw_core_assign_table_rows(msw_handle h, size_t *n_rows_out) {
+  return guarded(h, [&] {
+    if (!n_rows_out) throw Fail("msw_core_assign_table_rows: null n_rows_out");
+    assign_table_check(h, "msw_core_assign_table_rows", 0, 0);
+    *n_rows_out = h->assign.n_rows;
+  });
+}
+
+int msw_core_assign_table_block(msw_handle h, size_t row_begin, size_t row_end, const char **text_out, size_t *len_out) {
+  return guarded(h, [&] { assign_table_plain(h, row_begin, row_end, text_out, len_out); });
+}
+
+int msw_core_assign_table_block_gzip(msw_handle h, size_t row_begin, size_t row_end, const char **out, size_t *len_out,
+                                     size_t *text_len_out) {
+  return guarded(h, [&] { assign_table_gzip(h, row_begin, row_end, out, len_out, text_len_out); });
 }
 
 int msw_core_set_pack_schedule(msw_handle h, int enabled) {

@@ -259,6 +259,24 @@ struct FastqState {
   }
 };
 
+// ---- what msw_core_assign_reads keeps for msw_core_assign_table_* (host_assign.inc): MSW_ASSIGN_KEEP_TABLE.  Dropped by
+// a new likelihood, a solve, a bootstrap or an assign call without the flag ----------------------------------------------
+struct AssignState {
+  bool have = false;
+  uint32_t n_targets = 0;
+  size_t n_rows = 0;         // aligned reads: the table's rows
+  DevBuf<uint64_t> off;      // [E + 1] the ECs' (target slot, EC) pairs as the write pass left them: a CSR by EC
+  DevBuf<uint32_t> key;      // ... their target slots
+  DevBuf<uint32_t> id, ec;   // [n_rows] read id and EC of every row, ascending id (stable)
+  DevBuf<uint32_t> len;      // a block's text: row lengths, offsets, bytes, scan scratch
+  DevBuf<uint64_t> toff;
+  DevBuf<uint8_t> text, tmp;
+  void drop() {
+    have = false;
+    off.release(); key.release(); id.release(); ec.release(); len.release(); toff.release(); text.release(); tmp.release();
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -279,6 +297,7 @@ struct msw_core {
   GzState gz;
   InflateState inf;
   FastqState fastq;
+  AssignState assign;
   std::vector<uint64_t> lik_counts;  // first column of the last served likelihood file (host_likelihood_file.inc)
   Solver solver{&comm, &in_collective};  // on the handle's stream
 
