@@ -8,8 +8,17 @@
  * (msweep_amd/cpp/rcgpar_hip.hpp) turns non-zero into std::runtime_error so that
  * mSWEEP's try/catch blocks (src/mSWEEP.cpp:400-406, 506-511) behave as with rcgpar.
  *
- * Threading: one caller thread per handle (the reference calls from its single main
- * thread, src/mSWEEP.cpp:402,507).  A handle is bound to one HIP device.
+ * Threading: distinct handles may be used concurrently from distinct threads; one handle is used by one thread at
+ * a time (the reference calls from its single main thread, src/mSWEEP.cpp:402,507).  A handle is bound to one HIP
+ * device, and so are the alignments and read files made through it: every entry that takes one of them makes that
+ * device current for the calling thread before it touches HIP, so threads whose handles sit on different devices do
+ * not disturb each other, and a caller that uses HIP itself finds the device of the last handle it passed as the
+ * current one.  An object made through a handle (msw_alignment_read_device, msw_fastq_open) is used by the thread that
+ * uses the handle.  Error texts are per handle (msw_last_error(h)) or per thread (msw_last_error(NULL),
+ * msw_alignment_last_error, msw_comm_last_error).  Nothing else in the library is shared between handles except the
+ * code objects and the table of dynamic-LDS limits asked for (a limit belongs to a kernel on a device; the table only
+ * raises it, under a lock: msweep_amd/csrc/lds_grants.hpp).  The developer switches (MSWEEP_* in the environment) are
+ * read with getenv at the call: set them before the first thread starts.
  */
 #ifndef MSWEEP_CORE_H
 #define MSWEEP_CORE_H

@@ -12,15 +12,20 @@ FASTQ file themselves, gathered on the device where the file lies (Core.fastq_op
 `<dir>/unassigned_reads.bin`, the aligned reads no estimated group claims, and `<prefix>_reads_to_groups.tsv`, a 0/1 column
 per target for every aligned read, formatted on the device (Core.assign_reads_aln / assign_table_block).
 Every tab-separated column of the -i file is a grouping of its own: the estimation runs once per column
-(src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several."""
+(src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several.
+--samples FILE runs a whole manifest of samples (msweep_amd/samples.py) in this one process: -i is read once, every worker
+(--devices, one per entry) keeps one handle for its life and takes the next sample from a shared queue, and each sample's
+files are those a single run with its -o / --themisto / --extract-reads writes (run_samples below)."""
 import argparse
+import copy
 import math
 import os
 import sys
+import threading
 
 import numpy as np
 
-from . import binning, parallel
+from . import binning, parallel, samples
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
 from .likelihood import from_device_alignment, from_likelihood_file, read_likelihood_file  # noqa: F401 (read_likelihood_file: the host parser, under its name here)
 from .reference import output_path, read_references
@@ -67,8 +72,26 @@ def parse(argv):
     ap.add_argument("--compress", default="plaintext", help="plaintext or z (gzip, written on the device)")
     ap.add_argument("--compression-level", type=int, default=6, help="0 stores; 1 ... 9 run the same parse")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--samples", help="a manifest, one sample per line: <prefix> TAB <alignment files> [TAB <FASTQ files>]; "
+                                      "takes the place of -o / --themisto / --extract-reads")
+    ap.add_argument("--devices", help="with --samples: d0[,d1,...], one worker per entry (an entry may repeat)")
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
+
+
+_SAY_LOCK = threading.Lock()
+
+
+def _say(a, text):
+    """A message of the run to stderr.  Under --samples it carries `sample <prefix>: ` in front of its first line and is
+    written whole, so that the lines of two workers do not mix."""
+    tag = getattr(a, "sample_tag", "")
+    if not tag:
+        sys.stderr.write(text)
+        return
+    with _SAY_LOCK:
+        sys.stderr.write(tag + text)
+        sys.stderr.flush()
 
 
 def host_text():
@@ -282,9 +305,9 @@ def extract_reads(core, aln, targets, bin_ptr, reads, a):
                         how = "the device" if info["on_device"] else f"the host ({info['reason']})"
                         if info["on_device"] and info["n_members"]:
                             how += f" ({info['n_members']} BGZF members)"
-                        sys.stderr.write(f"note: {path}: gzip input inflated on {how}; {fq.info['n_records']} records\n")
+                        _say(a, f"note: {path}: gzip input inflated on {how}; {fq.info['n_records']} records\n")
                     else:
-                        sys.stderr.write(f"note: {path}: plain text; {fq.info['n_records']} records\n")
+                        _say(a, f"note: {path}: plain text; {fq.info['n_records']} records\n")
         # before any file is written: a read file of another sample has another number of records
         for path, fq in zip(a.extract_reads, a.fastqs):
             if fq.info["n_records"] != aln.n_reads:
@@ -301,7 +324,7 @@ def extract_reads(core, aln, targets, bin_ptr, reads, a):
                         for piece in fq.pieces(EXTRACT_PIECE):
                             f.write(piece)
     except (OSError, RuntimeError) as ex:      # (MswError is a RuntimeError)
-        sys.stderr.write(f"Extracting the reads failed:\n  {ex}\nexiting\n")
+        _say(a, f"Extracting the reads failed:\n  {ex}\nexiting\n")
         return 1
     return 0
 
@@ -340,12 +363,12 @@ def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
             bin_ptr, reads = res["bin_ptr"], res["reads"]
             if a.verbose:
                 c0, c1, c2 = (int(x) for x in res["class_reads"])
-                sys.stderr.write(f"note: {note}reads assigned to one group: {c1}, to several: {c2}, to none: {c0}, "
+                _say(a, f"note: {note}reads assigned to one group: {c1}, to several: {c2}, to none: {c0}, "
                                  f"of {c0 + c1 + c2} aligned reads\n")
         else:
             bin_ptr, reads, _ = core.bin_reads_aln(aln, rows, binning.thresholds(rows, theta))
     except (binning.BinningError, MswError) as ex:
-        sys.stderr.write(f"Binning the reads failed:\n  {ex}\nexiting\n")
+        _say(a, f"Binning the reads failed:\n  {ex}\nexiting\n")
         return 1
     bins = list(targets) + ([binning.UNASSIGNED] if a.write_unassigned else [])    # the unassigned bin is the last one
     for k, name in enumerate(bins):
@@ -357,22 +380,168 @@ def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
             else:
                 binning.write_bin(binning.bin_path(a.prefix, name), ids)
         except (OSError, MswError) as ex:
-            sys.stderr.write(f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
+            _say(a, f"Writing the bin for target group {name} failed:\n  {ex}\nexiting\n")
             return 1
     if a.write_assignment_table:
         try:
             write_assignment_table(core, table_path, targets, a)
         except (OSError, MswError) as ex:
-            sys.stderr.write(f"Writing the assignment table failed:\n  {ex}\nexiting\n")
+            _say(a, f"Writing the assignment table failed:\n  {ex}\nexiting\n")
             return 1
     if a.extract_reads:
         return extract_reads(core, aln, bins, bin_ptr, reads, a)
     return 0
 
 
+def read_indicators(a):
+    """every tab-separated column of -i is a grouping of its own (include/Reference.hpp:67-94); the estimation runs
+    once per column (src/mSWEEP.cpp:282), from ONE resident alignment"""
+    with open(a.indicators) as f:
+        gs = read_references(f)
+    if a.verbose and len(gs) > 1:
+        sys.stderr.write(f"  read {len(gs)} groupings\n")      # src/mSWEEP.cpp:265-267
+    return gs
+
+
+def read_sample(a, core, files, n_targets):
+    """The reader on the device (msw_alignment_read_device): text -> equivalence classes in HBM, consumed there by the
+    likelihood build; the reference's messages for text it does not take.  Once per sample, in front of the grouping
+    loop: the line count of -i is the same for every column."""
+    if not files:
+        raise RuntimeError("no pseudoalignment files given")
+    aln = core.read_alignment(files, n_targets, a.themisto_mode)
+    if a.verbose:
+        # gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
+        for path, info in zip(files, core.last_inflate()):
+            if info["payload_bytes"] or info["fallback_reason"]:
+                how = "the device" if info["on_device"] else f"the host ({info['reason']})"
+                if info["on_device"] and info["n_members"]:
+                    how += f" ({info['n_members']} BGZF members)"
+                _say(a, f"note: {path}: gzip input inflated on {how}\n")
+    return aln
+
+
+def run_groupings(a, core, aln, groupings, algo, prec):
+    """The grouping loop (src/mSWEEP.cpp:282): build, outputs, solve, bins, bootstrap per column on the one handle -- every
+    build replaces the resident likelihood and all that was derived from the one before (include/msweep_core.h).  A
+    grouping that fails ends the sample; the files of the groupings before it stay.  Returns the exit status."""
+    try:
+        for index, grouping in enumerate(groupings):
+            rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
+            if rc:
+                return rc
+    finally:
+        for fq in list(a.fastqs):      # --extract-reads: the read files go at the end of the sample
+            fq.close()
+    return 0
+
+
+def _algo_prec(a):
+    algo = ALGO_RCG if a.algorithm in ("rcggpu", "rcgcpu") else ALGO_EM   # anything else -> em (src/mSWEEP.cpp:200)
+    # (--emprecision float: fp32 kernels where the layout allows, msweep_amd/csrc/em_f32_kernels.hpp; the library
+    # reports which through msw_timing::em_float_kernels)
+    return algo, PREC_FLOAT if a.emprecision == "float" else PREC_DOUBLE
+
+
+# Workers of --samples without --devices.  One: a second worker on the same device did not beat one by more than the
+# spread of the repeats at both measured shapes (profiles/batch_timing.txt; DESIGN.md 7i).
+DEFAULT_WORKERS = 1
+
+
+def run_samples(a, manifest, devices):
+    """--samples: the manifest on resident handles.  Each worker owns one handle for its life, takes the next sample from
+    the shared queue in manifest order, reads it, runs the grouping loop, closes its alignment and read files and trims
+    the handle (msw_core_trim: one sample's reader temporaries do not stay under the next).  The first failure stops the
+    queue: samples in flight finish, their files and those of the finished samples stay, the status is 1 -- after an
+    error that may come from the device nothing more is started on it."""
+    try:
+        groupings = read_indicators(a)
+    except (RuntimeError, OSError) as ex:
+        sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
+        return 1
+    cores = []
+    try:
+        for d in devices:
+            cores.append(Core(d))
+    except MswError as ex:
+        sys.stderr.write(f"Initialising the GPU failed:\n  {ex}\nexiting\n")
+        return 1
+    if a.algorithm == "rcgcpu" and a.verbose:
+        sys.stderr.write("note: --algorithm rcgcpu is served by the GPU RCG kernels (same algorithm as rcggpu)\n")
+    algo, prec = _algo_prec(a)
+    try:
+        for core in cores:
+            core.set_pack_schedule(a.iters >= 5)
+    except MswError as ex:
+        sys.stderr.write(f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
+        return 1
+    lock = threading.Lock()
+    state = {"next": 0, "finished": 0, "failed": 0}
+    n_targets = len(groupings[0].group_indicators)
+
+    def one(core, s):
+        sa = copy.copy(a)
+        sa.prefix, sa.extract_reads, sa.fastqs, sa.sample_tag = s.prefix, s.fastqs, [], f"sample {s.prefix}: "
+        try:
+            try:
+                aln = read_sample(sa, core, s.files, n_targets)
+            except (RuntimeError, OSError, MswError) as ex:
+                _say(sa, f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
+                return 1
+            try:
+                return run_groupings(sa, core, aln, groupings, algo, prec)
+            finally:
+                aln.close()
+        except Exception as ex:      # what a single run would end on with a traceback: this sample's failure
+            _say(sa, f"Running the sample failed:\n  {type(ex).__name__}: {ex}\nexiting\n")
+            return 1
+
+    def worker(core):
+        while True:
+            with lock:
+                if state["failed"] or state["next"] >= len(manifest):
+                    return
+                s = manifest[state["next"]]
+                state["next"] += 1
+            rc = one(core, s)
+            if rc == 0:
+                try:
+                    core.trim()
+                except MswError as ex:
+                    _say(a, f"sample {s.prefix}: Trimming the handle failed:\n  {ex}\nexiting\n")
+                    rc = 1
+            with lock:
+                state["failed" if rc else "finished"] += 1
+
+    threads = [threading.Thread(target=worker, args=(core,)) for core in cores]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for core in cores:
+        core.close()
+    if state["failed"] or a.verbose:
+        sys.stderr.write(f"samples: {state['finished']} finished, {state['failed']} failed, "
+                         f"{len(manifest) - state['finished'] - state['failed']} not started\n")
+    return 1 if state["failed"] else 0
+
+
 def main(argv=None):
     a = parse(sys.argv[1:] if argv is None else argv)
     aln = None
+    manifest = None
+    if a.samples is not None or a.devices is not None:
+        # --samples: everything about the manifest is judged before the GPU is touched (msweep_amd/samples.py)
+        given = [f for f, v in (("--themisto", a.themisto), ("--themisto-1", a.themisto_1), ("--themisto-2", a.themisto_2),
+                                ("-o", a.prefix), ("--read-likelihood", a.read_likelihood), ("--print-probs", a.print_probs),
+                                ("--extract-reads", a.extract_reads is not None)) if v]
+        try:
+            manifest, devices = samples.from_args(given, a.samples, a.devices, a.bin_reads)
+        except samples.ManifestError as ex:
+            sys.stderr.write(f"Parsing arguments failed:\n  {ex}\nexiting\n")
+            return 1
+        if devices is None:
+            devices = [a.device] * DEFAULT_WORKERS
     # before the GPU is touched: the reference's words (src/OutfileDesignator.cpp:30-62) for what this core does not build
     if a.compress not in ("plaintext", "z"):
         sys.stderr.write(f"Parsing arguments failed:\n  unsupported compression type {a.compress} "
@@ -382,7 +551,7 @@ def main(argv=None):
         sys.stderr.write(f"Parsing arguments failed:\n  unsupported compression level {a.compression_level} "
                          "(this core builds z only, levels 0 ... 9)\nexiting\n")
         return 1
-    if not a.prefix:
+    if not a.prefix and manifest is None:
         a.compress = "plaintext"        # what goes to stdout stays plain
     if a.bin_reads and a.read_likelihood:
         # "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
@@ -400,21 +569,15 @@ def main(argv=None):
         if any(not p for p in a.extract_reads):
             sys.stderr.write("Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n")
             return 1
+    if manifest is not None:
+        return run_samples(a, manifest, devices)
     a.fastqs = []     # the read files of --extract-reads, resident from the first grouping that bins
-    def read_indicators():
-        # every tab-separated column of -i is a grouping of its own (include/Reference.hpp:67-94); the estimation runs
-        # once per column (src/mSWEEP.cpp:282), here from ONE resident alignment
-        with open(a.indicators) as f:
-            gs = read_references(f)
-        if a.verbose and len(gs) > 1:
-            sys.stderr.write(f"  read {len(gs)} groupings\n")      # src/mSWEEP.cpp:265-267
-        return gs
     groupings = None
     if a.read_likelihood:
         # more than one grouping is refused in the reference's words (src/mSWEEP.cpp:360-362), before the GPU is touched:
         # with this flag the indicators are read first
         try:
-            groupings = read_indicators()
+            groupings = read_indicators(a)
         except (RuntimeError, OSError) as ex:
             sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
             return 1
@@ -429,23 +592,10 @@ def main(argv=None):
         return 1
     try:
         if groupings is None:
-            groupings = read_indicators()
+            groupings = read_indicators(a)
         if not a.read_likelihood:
             files = a.themisto.split(",") if a.themisto else [x for x in (a.themisto_1, a.themisto_2) if x]
-            if not files:
-                raise RuntimeError("no pseudoalignment files given")
-            # the reader on the device (msw_alignment_read_device): text -> equivalence classes in HBM, consumed there
-            # by the likelihood build; the reference's messages for text it does not take
-            # -- once, in front of the grouping loop: the line count of -i is the same for every column
-            aln = core.read_alignment(files, len(groupings[0].group_indicators), a.themisto_mode)
-            if a.verbose:
-                # gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
-                for path, info in zip(files, core.last_inflate()):
-                    if info["payload_bytes"] or info["fallback_reason"]:
-                        how = "the device" if info["on_device"] else f"the host ({info['reason']})"
-                        if info["on_device"] and info["n_members"]:
-                            how += f" ({info['n_members']} BGZF members)"
-                        sys.stderr.write(f"note: {path}: gzip input inflated on {how}\n")
+            aln = read_sample(a, core, files, len(groupings[0].group_indicators))
     except (RuntimeError, OSError, MswError) as ex:
         sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
         return 1
@@ -454,27 +604,16 @@ def main(argv=None):
         # on the GPU -- there is no CPU path here
         if a.verbose:
             sys.stderr.write("note: --algorithm rcgcpu is served by the GPU RCG kernels (same algorithm as rcggpu)\n")
-    algo = ALGO_RCG if a.algorithm in ("rcggpu", "rcgcpu") else ALGO_EM   # anything else -> em (src/mSWEEP.cpp:200)
-    prec = PREC_FLOAT if a.emprecision == "float" else PREC_DOUBLE
-    # (--emprecision float: fp32 kernels where the layout allows, msweep_amd/csrc/em_f32_kernels.hpp; the library
-    # reports which through msw_timing::em_float_kernels)
+    algo, prec = _algo_prec(a)
     try:
         # ordering the cells for the LDS banks pays from about the 1 000th iteration on: bootstrap runs (msw_core_set_pack_schedule)
         core.set_pack_schedule(a.iters >= 5)
     except MswError as ex:
         sys.stderr.write(f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
         return 1
-    # the grouping loop (src/mSWEEP.cpp:282): build, outputs, solve, bins, bootstrap per column on the one handle -- every
-    # build replaces the resident likelihood and all that was derived from the one before (include/msweep_core.h).  A
-    # grouping that fails ends the run; the files of the groupings before it stay.
-    try:
-        for index, grouping in enumerate(groupings):
-            rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
-            if rc:
-                return rc
-    finally:
-        for fq in list(a.fastqs):      # --extract-reads: the read files go at the end of the run
-            fq.close()
+    rc = run_groupings(a, core, aln, groupings, algo, prec)
+    if rc:
+        return rc
     core.close()
     return 0
 
@@ -493,7 +632,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
             ec_counts, info = lik.ec_counts, lik.file_info
             if a.verbose:
                 how = f"the device ({info['n_host_cells']} cells on the host)" if info["served"] else f"the host ({info['reason_text']})"
-                sys.stderr.write(f"note: {note}{a.read_likelihood}: likelihood file parsed on {how}\n")
+                _say(a, f"note: {note}{a.read_likelihood}: likelihood file parsed on {how}\n")
             n_reads = total_reads = int(ec_counts.sum())
         else:
             if aln.n_ecs == 0:
@@ -503,7 +642,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
             ec_counts = aln.ec_counts()
             n_reads = aln.n_reads
     except (MswError, RuntimeError, OSError, ValueError) as ex:
-        sys.stderr.write(f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
+        _say(a, f"Building the log-likelihood array failed:\n  {ex}\nexiting\n")
         return 1
     try:
         if a.write_likelihood_bitseq:
@@ -517,7 +656,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
             with _open_out(core, path("likelihoods.tsv"), a) as f:
                 write_likelihood_file(f, ec_counts, lik)
     except (MswError, RuntimeError, OSError) as ex:
-        sys.stderr.write(f"Writing the likelihood to file failed:\n  {ex}\nexiting\n")
+        _say(a, f"Writing the likelihood to file failed:\n  {ex}\nexiting\n")
         return 1
     if a.no_fit_model:
         return 0
@@ -526,7 +665,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
     if a.alphas:
         prior = np.array([float(x) for x in a.alphas.split(",")])
         if len(prior) != G:
-            sys.stderr.write("Error: --alphas must have the same number of values as there are groups.")
+            _say(a, "Error: --alphas must have the same number of values as there are groups.")
             return 1
     total = int(ec_counts.sum())
     sample = BootstrapSample(n_reads, total, a.iters) if a.iters > 0 else PlainSample(n_reads, total)
@@ -536,10 +675,10 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
         if a.verbose:
             t = core.trace(min(res["iters"], 4096))
             for k in range(0, t["n"], 5):
-                sys.stderr.write(f"  {note}iter: {k}, bound: {t['bound'][k]:g}, |g|: {t['newnorm'][k]:g}\n")
+                _say(a, f"  {note}iter: {k}, bound: {t['bound'][k]:g}, |g|: {t['newnorm'][k]:g}\n")
         sample.store_abundances(res["theta"])
     except MswError as ex:
-        sys.stderr.write(f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
+        _say(a, f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
         return 1
     if a.bin_reads:
         # before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
@@ -561,7 +700,7 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
             for row in thetas:
                 sample.store_abundances(row)
     except MswError as ex:
-        sys.stderr.write(f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
+        _say(a, f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
         return 1
     names = grouping.get_names()
     mask = lik.groups_considered()

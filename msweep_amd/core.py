@@ -309,6 +309,14 @@ class DeviceAlignment:
             self._counts = out
         return self._counts
 
+    def close(self):
+        """Gives the alignment's memory back now, not when the last reference goes (a driver that reads one sample after
+        the other on one handle).  Arrays handed out by arrays() keep it alive as before."""
+        if self._arrays is None and self._owner._h:
+            self._L.msw_alignment_destroy(self._owner._h)
+            self._owner._h = None
+        self._h = None
+
     def arrays(self):
         if self._arrays is None:
             self._arrays = _alignment_views(self._L, self._h, self._owner, self.n_ecs, self.n_hits, self.n_aligned, self.n_reads)

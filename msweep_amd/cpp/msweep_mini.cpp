@@ -21,6 +21,9 @@
 // Every tab-separated column of the -i file is a grouping of its own and the whole estimation runs once per column
 // (src/mSWEEP.cpp:282) -- from ONE read of the pseudoalignment, whose classes stay in device memory: run_grouping() is the
 // body of that loop, out_path() names its files (`<prefix>_<i>_...` when there are several; tests/test_gpu_groupings.py).
+// --samples FILE runs a whole manifest of samples (samples_manifest.hpp) in this one process: -i is read once, every worker
+// (--devices, one std::thread per entry) keeps one handle for its life and takes the next sample from a shared queue, and
+// each sample's files are those a single run with its -o / --themisto / --extract-reads writes (run_samples).
 //
 //   g++ -std=c++17 -O2 -o msweep_mini msweep_mini.cpp -L.. -lmsweep_core -Wl,-rpath,..
 #include <algorithm>
@@ -34,6 +37,7 @@
 #include <iostream>
 #include <iterator>
 #include <map>
+#include <mutex>
 #include <random>
 #include <sstream>
 #include <stdexcept>
@@ -43,6 +47,7 @@
 #include <vector>
 
 #include "../../include/msweep_core.h"
+#include "samples_manifest.hpp"
 
 namespace {
 
@@ -66,6 +71,30 @@ struct Args {
   std::vector<std::string> extract_reads;  // --extract-reads A[,B,...]: the FASTQ files the bins are extracted from
   std::string compress = "plaintext";  // or "z"
   int compression_level = 6;           // 0 stores; 1 ... 9 run the core's one parse
+  // --samples FILE / --devices d0[,d1,...]: a manifest of samples on resident handles, one worker per device entry
+  bool have_samples = false, have_devices = false;
+  std::string samples, devices;
+  std::vector<std::string> given;  // the flags of msw_samples::conflicts() that the command line holds
+};
+
+// A message of the run to stderr, written whole when the object goes: under --samples the lines of two workers do not mix,
+// and the worker's `sample <prefix>: ` (t_tag) stands in front of the message's first line.
+thread_local std::string t_tag;
+std::mutex g_err_mu;
+struct Msg {
+  std::ostringstream os;
+  template <class T>
+  Msg &operator<<(const T &v) {
+    os << v;
+    return *this;
+  }
+  ~Msg() {
+    const std::string s = os.str();
+    if (s.empty()) return;
+    std::lock_guard<std::mutex> g(g_err_mu);
+    std::cerr << t_tag << s;
+    std::cerr.flush();
+  }
 };
 
 std::vector<std::string> split(const std::string &s, char d) {
@@ -85,6 +114,8 @@ Args parse(int argc, char **argv) {
       if (i + 1 >= argc) throw std::runtime_error("missing value for " + k);
       return argv[++i];
     };
+    for (const std::string &f : msw_samples::conflicts())
+      if (k == f) a.given.push_back(k);
     if (k == "--themisto") a.themisto = split(val(), ',');
     else if (k == "--themisto-1") t1 = val();
     else if (k == "--themisto-2") t2 = val();
@@ -117,6 +148,13 @@ Args parse(int argc, char **argv) {
     else if (k == "--write-unassigned") a.write_unassigned = true;
     else if (k == "--write-assignment-table") a.write_assignment_table = true;
     else if (k == "--compress") a.compress = val();
+    else if (k == "--samples") {
+      a.samples = val();
+      a.have_samples = true;
+    } else if (k == "--devices") {
+      a.devices = val();
+      a.have_devices = true;
+    }
     else if (k == "--compression-level") a.compression_level = std::stoi(val());
     else if (k == "--target-groups") {
       a.target_groups = split(val(), ',');
@@ -435,12 +473,13 @@ int extract_reads(const Args &a, msw_handle h, size_t n_reads, std::vector<msw_f
         fastq_records.push_back(info.n_records);
         if (a.verbose) {
           const msw_inflate_info &f = info.inflate;
-          std::cerr << "note: " << path << ": ";
-          if (!f.payload_bytes && !f.fallback_reason) std::cerr << "plain text";
-          else if (f.on_device && f.n_members) std::cerr << "gzip input inflated on the device (" << f.n_members << " BGZF members)";
-          else if (f.on_device) std::cerr << "gzip input inflated on the device";
-          else std::cerr << "gzip input inflated on the host (" << why[f.fallback_reason >= 0 && f.fallback_reason < 9 ? f.fallback_reason : 0] << ")";
-          std::cerr << "; " << info.n_records << " records\n";
+          Msg m;
+          m << "note: " << path << ": ";
+          if (!f.payload_bytes && !f.fallback_reason) m << "plain text";
+          else if (f.on_device && f.n_members) m << "gzip input inflated on the device (" << f.n_members << " BGZF members)";
+          else if (f.on_device) m << "gzip input inflated on the device";
+          else m << "gzip input inflated on the host (" << why[f.fallback_reason >= 0 && f.fallback_reason < 9 ? f.fallback_reason : 0] << ")";
+          m << "; " << info.n_records << " records\n";
         }
       }
     }
@@ -462,7 +501,7 @@ int extract_reads(const Args &a, msw_handle h, size_t n_reads, std::vector<msw_f
         if (!f.good()) throw std::runtime_error("cannot write " + path);
       }
   } catch (const std::exception &ex) {
-    std::cerr << "Extracting the reads failed:\n  " << ex.what() << "\nexiting\n";
+    Msg() << "Extracting the reads failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
   return 0;
@@ -518,7 +557,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
                                          nullptr, cls));
       if (a.write_unassigned) names.push_back("unassigned_reads");  // the unassigned bin is the last one
       if (a.verbose)
-        std::cerr << "note: " << note << "reads assigned to one group: " << cls[1] << ", to several: " << cls[2]
+        Msg() << "note: " << note << "reads assigned to one group: " << cls[1] << ", to several: " << cls[2]
                   << ", to none: " << cls[0] << ", of " << cls[0] + cls[1] + cls[2] << " aligned reads\n";
     } else {
       std::vector<double> thr(rows.size());
@@ -529,7 +568,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
       check(h, msw_core_bin_reads_aln(h, aln, rows.data(), thr.data(), rows.size(), bin_ptr.data(), reads.data(), nullptr));
     }
   } catch (const std::exception &ex) {
-    std::cerr << "Binning the reads failed:\n  " << ex.what() << "\nexiting\n";
+    Msg() << "Binning the reads failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
   const size_t n = names.size(), nt = std::min(n, writer_threads());
@@ -549,7 +588,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
         f.write(ids);
         f.close();
       } catch (const std::exception &ex) {
-        std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << ex.what() << "\nexiting\n";
+        Msg() << "Writing the bin for target group " << names[k] << " failed:\n  " << ex.what() << "\nexiting\n";
         return 1;
       }
     }
@@ -563,7 +602,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
     for (auto &th : pool) th.join();
     for (size_t k = 0; k < n; ++k)
       if (!err[k].empty()) {
-        std::cerr << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
+        Msg() << "Writing the bin for target group " << names[k] << " failed:\n  " << err[k] << "\nexiting\n";
         return 1;
       }
   }
@@ -571,7 +610,7 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
     try {
       write_assignment_table(a, h, table_path, targets);
     } catch (const std::exception &ex) {
-      std::cerr << "Writing the assignment table failed:\n  " << ex.what() << "\nexiting\n";
+      Msg() << "Writing the assignment table failed:\n  " << ex.what() << "\nexiting\n";
       return 1;
     }
   }
@@ -762,9 +801,10 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       if (a.verbose) {
         static const char *const why[] = {"none", "forced", "open / read", "bad byte", "bad token", "column count", "empty",
                                           "too many host cells", "range error", "memory", "too many lines"};
-        std::cerr << "note: " << note << a.read_likelihood << ": likelihood file parsed on ";
-        if (lf.served) std::cerr << "the device (" << lf.n_host_cells << " cells on the host)\n";
-        else std::cerr << "the host (" << why[lf.reason >= 0 && lf.reason < 11 ? lf.reason : 0] << ")\n";
+        Msg m;
+        m << "note: " << note << a.read_likelihood << ": likelihood file parsed on ";
+        if (lf.served) m << "the device (" << lf.n_host_cells << " cells on the host)\n";
+        else m << "the host (" << why[lf.reason >= 0 && lf.reason < 11 ? lf.reason : 0] << ")\n";
       }
       if (lf.served) {
         n_ecs = (size_t)lf.n_ecs;
@@ -790,7 +830,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       // (the pseudoalignment stays: the next grouping is built from it, and --bin-reads reads its classes)
     }
   } catch (const std::exception &ex) {
-    std::cerr << "Building the log-likelihood array failed:\n  " << ex.what() << "\nexiting\n";
+    Msg() << "Building the log-likelihood array failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
   try {
@@ -805,7 +845,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
     }
   } catch (const std::exception &ex) {
-    std::cerr << "Writing the likelihood to file failed:\n  " << ex.what() << "\nexiting\n";
+    Msg() << "Writing the likelihood to file failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
   if (a.no_fit_model) return 0;  // src/mSWEEP.cpp:385-386
@@ -814,7 +854,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
     // checked against THIS grouping's group count when it is reached (src/mSWEEP.cpp:392-396)
     const auto parts = split(a.alphas, ',');
     if (parts.size() != n_kept) {
-      std::cerr << "Error: --alphas must have the same number of values as there are groups.";
+      Msg() << "Error: --alphas must have the same number of values as there are groups.";
       return 1;
     }
     for (size_t i = 0; i < n_kept; ++i) prior[i] = std::stod(parts[i]);
@@ -839,7 +879,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       char buf[128];
       for (size_t k = 0; k < got; k += 5) {
         snprintf(buf, sizeof buf, "iter: %zu, bound: %g, |g|: %g\n", k, b[k], nn[k]);
-        std::cerr << "  " << note << buf;
+        Msg() << "  " << note << buf;
       }
     }
     results.push_back(theta);
@@ -882,7 +922,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       }
     }
   } catch (const std::exception &ex) {
-    std::cerr << "Estimating relative abundances failed:\n  " << ex.what() << "\nexiting\n";
+    Msg() << "Estimating relative abundances failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
   }
 
@@ -924,6 +964,133 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
   return 0;
 }
 
+// One sample's pseudoalignment into r.  The reader runs ON THE DEVICE (msw_alignment_read_device: text -> equivalence
+// classes in HBM) and the likelihood builds consume its arrays there (msw_core_build_likelihood_aln); only the classes'
+// read counts come to the host.  Once per sample, in front of the grouping loop: the line count of -i is the same for
+// every column.  Throws with the reference's messages.
+void read_sample(const Args &a, Run &r, size_t n_targets) {
+  msw_handle h = r.h;
+  if (a.themisto.empty()) throw std::runtime_error("no pseudoalignment files given");
+  if (a.mode != "intersection" && a.mode != "union") throw std::runtime_error("Unrecognized option `" + a.mode + "` for --themisto-mode");
+  std::vector<const char *> paths;
+  for (auto &p : a.themisto) paths.push_back(p.c_str());
+  if (msw_alignment_read_device(h, paths.data(), paths.size(), n_targets, a.mode == "union" ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION,
+                                &r.aln))
+    throw std::runtime_error(msw_alignment_last_error());
+  if (a.verbose) {
+    // gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
+    static const char *const why[] = {"none", "forced", "header", "probe mismatch", "chunk status", "crc", "trailing bytes", "memory", "long span"};
+    std::vector<msw_inflate_info> info(paths.size());
+    size_t n_info = 0;
+    if (msw_alignment_last_inflate(h, info.data(), info.size(), &n_info) == 0)
+      for (size_t i = 0; i < std::min(n_info, info.size()); ++i) {
+        if (!info[i].payload_bytes && !info[i].fallback_reason) continue;
+        Msg m;
+        m << "note: " << paths[i] << ": gzip input inflated on ";
+        if (info[i].on_device && info[i].n_members) m << "the device (" << info[i].n_members << " BGZF members)\n";
+        else if (info[i].on_device) m << "the device\n";
+        else m << "the host (" << why[info[i].fallback_reason >= 0 && info[i].fallback_reason < 9 ? info[i].fallback_reason : 0] << ")\n";
+      }
+  }
+  size_t n_hits = 0, n_aligned = 0;
+  msw_alignment_shape(r.aln, &r.n_ecs, &r.n_reads, &n_hits, &n_aligned);
+  r.ec_counts.resize(r.n_ecs);
+  msw_alignment_export(r.aln, nullptr, nullptr, r.ec_counts.data(), nullptr, nullptr);
+}
+
+// Workers of --samples without --devices.  One: a second worker on the same device did not beat one by more than the
+// spread of the repeats at both measured shapes (profiles/batch_timing.txt).
+constexpr size_t kDefaultWorkers = 1;
+
+// --samples: the manifest on resident handles.  Each worker owns one handle for its life, takes the next sample from the
+// shared queue in manifest order, reads it, runs the grouping loop, closes its alignment and read files and trims the
+// handle (msw_core_trim: one sample's reader temporaries do not stay under the next).  The first failure stops the queue:
+// samples in flight finish, their files and those of the finished samples stay, the status is 1 -- after an error that may
+// come from the device nothing more is started on it.  The same steps as msweep_amd/__main__.py run_samples.
+int run_samples(const Args &a, const std::vector<msw_samples::Sample> &manifest, const std::vector<int> &devices) {
+  std::vector<Grouping> groupings;
+  try {
+    groupings = read_groupings(a.indicators);
+    if (a.verbose && groupings.size() > 1) std::cerr << "  read " << groupings.size() << " groupings\n";  // src/mSWEEP.cpp:265-267
+  } catch (const std::exception &ex) {
+    std::cerr << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
+  }
+  std::vector<msw_handle> handles;
+  auto destroy_all = [&] {
+    for (msw_handle h : handles) msw_core_destroy(h);
+  };
+  for (int d : devices) {
+    msw_handle h = nullptr;
+    if (msw_core_create(d, &h) != 0) {
+      std::cerr << "Initialising the GPU failed:\n  " << msw_last_error(nullptr) << "\nexiting\n";
+      destroy_all();
+      return 1;
+    }
+    handles.push_back(h);
+  }
+  if (a.algorithm == "rcgcpu" && a.verbose)
+    std::cerr << "note: --algorithm rcgcpu is served by the GPU RCG kernels (same algorithm as rcggpu)\n";
+  const int algo = (a.algorithm == "rcggpu" || a.algorithm == "rcgcpu") ? MSW_ALGO_RCG : MSW_ALGO_EM;
+  const int prec = a.emprecision == "float" ? MSW_PREC_FLOAT : MSW_PREC_DOUBLE;
+  for (msw_handle h : handles)
+    if (msw_core_set_pack_schedule(h, a.iters >= 5 ? 1 : 0) != 0) {
+      std::cerr << "Building the log-likelihood array failed:\n  " << msw_last_error(h) << "\nexiting\n";
+      destroy_all();
+      return 1;
+    }
+  msw_samples::Queue queue(manifest.size());
+  auto one = [&](msw_handle h, const msw_samples::Sample &s) -> int {
+    Args sa = a;
+    sa.prefix = s.prefix;
+    sa.themisto = s.files;
+    sa.have_extract_reads = s.have_fastqs;
+    sa.extract_reads = s.fastqs;
+    Run r;
+    r.h = h;
+    r.n_groupings = groupings.size();
+    r.algo = algo;
+    r.prec = prec;
+    int rc = 0;
+    try {
+      try {
+        read_sample(sa, r, groupings[0].indicators.size());
+      } catch (const std::exception &ex) {
+        Msg() << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
+        rc = 1;
+      }
+      for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(sa, r, groupings[i], i);
+    } catch (const std::exception &ex) {  // what a single run would end on uncaught: this sample's failure
+      Msg() << "Running the sample failed:\n  " << ex.what() << "\nexiting\n";
+      rc = 1;
+    }
+    for (msw_fastq_t fq : r.fastqs) msw_fastq_close(fq);
+    msw_alignment_destroy(r.aln);
+    if (rc == 0 && msw_core_trim(h) != 0) {
+      Msg() << "Trimming the handle failed:\n  " << msw_last_error(h) << "\nexiting\n";
+      rc = 1;
+    }
+    return rc;
+  };
+  std::vector<std::thread> workers;
+  for (msw_handle h : handles)
+    workers.emplace_back([&, h] {
+      size_t i = 0;
+      while (queue.next(i)) {
+        t_tag = "sample " + manifest[i].prefix + ": ";
+        const int rc = one(h, manifest[i]);
+        t_tag.clear();
+        queue.done(rc == 0);
+      }
+    });
+  for (auto &w : workers) w.join();
+  destroy_all();
+  if (queue.failed() || a.verbose)
+    std::cerr << "samples: " << queue.finished() << " finished, " << queue.failed() << " failed, " << queue.not_started()
+              << " not started\n";
+  return queue.failed() ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -933,6 +1100,18 @@ int main(int argc, char **argv) {
   } catch (const std::exception &ex) {
     std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
+  }
+  std::vector<msw_samples::Sample> manifest;
+  std::vector<int> devices;
+  if (a.have_samples || a.have_devices) {
+    // --samples: everything about the manifest is judged before the GPU is touched (samples_manifest.hpp)
+    try {
+      manifest = msw_samples::from_args(a.given, a.have_samples, a.samples, a.have_devices, a.devices, a.bin_reads, devices);
+    } catch (const std::exception &ex) {
+      std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
+      return 1;
+    }
+    if (devices.empty()) devices.assign(kDefaultWorkers, a.gpu);
   }
   // before the GPU is touched: the reference's words (src/OutfileDesignator.cpp:30-62) for what this core does not build
   if (a.compress != "plaintext" && a.compress != "z") {
@@ -945,7 +1124,7 @@ int main(int argc, char **argv) {
               << " (this core builds z only, levels 0 ... 9)\nexiting\n";
     return 1;
   }
-  if (a.prefix.empty()) a.compress = "plaintext";  // what goes to stdout stays plain
+  if (a.prefix.empty() && !a.have_samples) a.compress = "plaintext";  // what goes to stdout stays plain
   if (a.bin_reads && !a.read_likelihood.empty()) {
     // "Can't be used with --bin-reads" (src/mSWEEP.cpp:115): the reads of a class are not in a likelihood file
     std::cerr << "Binning the reads failed:\n  --read-likelihood can't be used with --bin-reads\nexiting\n";
@@ -969,6 +1148,7 @@ int main(int argc, char **argv) {
         return 1;
       }
   }
+  if (a.have_samples) return run_samples(a, manifest, devices);
   // every tab-separated column of -i is a grouping of its own; the estimation runs once per column
   // (src/mSWEEP.cpp:282), here from ONE resident alignment
   std::vector<Grouping> groupings;
@@ -991,8 +1171,6 @@ int main(int argc, char **argv) {
     }
   }
   Run r;
-  // The reader runs ON THE DEVICE (msw_alignment_read_device: text -> equivalence classes in HBM) and the likelihood
-  // builds consume its arrays there (msw_core_build_likelihood_aln); only the classes' read counts come to the host.
   if (msw_core_create(a.gpu, &r.h) != 0) {
     std::cerr << "Initialising the GPU failed:\n  " << msw_last_error(nullptr) << "\nexiting\n";
     return 1;
@@ -1001,35 +1179,8 @@ int main(int argc, char **argv) {
   try {
     if (groupings.empty()) read_indicators();
     r.n_groupings = groupings.size();
-    if (a.read_likelihood.empty()) {  // (--read-likelihood needs no pseudoalignments: src/mSWEEP.cpp:296-370)
-      if (a.themisto.empty()) throw std::runtime_error("no pseudoalignment files given");
-      if (a.mode != "intersection" && a.mode != "union")
-        throw std::runtime_error("Unrecognized option `" + a.mode + "` for --themisto-mode");
-      std::vector<const char *> paths;
-      for (auto &p : a.themisto) paths.push_back(p.c_str());
-      // once, in front of the grouping loop: the line count of -i is the same for every column
-      if (msw_alignment_read_device(h, paths.data(), paths.size(), groupings[0].indicators.size(),
-                                    a.mode == "union" ? MSW_MERGE_UNION : MSW_MERGE_INTERSECTION, &r.aln))
-        throw std::runtime_error(msw_alignment_last_error());
-      if (a.verbose) {
-        // gzip input: inflated by the kernels, or by zlib where their result could not be vouched for
-        static const char *const why[] = {"none", "forced", "header", "probe mismatch", "chunk status", "crc", "trailing bytes", "memory", "long span"};
-        std::vector<msw_inflate_info> info(paths.size());
-        size_t n_info = 0;
-        if (msw_alignment_last_inflate(h, info.data(), info.size(), &n_info) == 0)
-          for (size_t i = 0; i < std::min(n_info, info.size()); ++i) {
-            if (!info[i].payload_bytes && !info[i].fallback_reason) continue;
-            std::cerr << "note: " << paths[i] << ": gzip input inflated on ";
-            if (info[i].on_device && info[i].n_members) std::cerr << "the device (" << info[i].n_members << " BGZF members)\n";
-            else if (info[i].on_device) std::cerr << "the device\n";
-            else std::cerr << "the host (" << why[info[i].fallback_reason >= 0 && info[i].fallback_reason < 9 ? info[i].fallback_reason : 0] << ")\n";
-          }
-      }
-      size_t n_hits = 0, n_aligned = 0;
-      msw_alignment_shape(r.aln, &r.n_ecs, &r.n_reads, &n_hits, &n_aligned);
-      r.ec_counts.resize(r.n_ecs);
-      msw_alignment_export(r.aln, nullptr, nullptr, r.ec_counts.data(), nullptr, nullptr);
-    }
+    // (--read-likelihood needs no pseudoalignments: src/mSWEEP.cpp:296-370)
+    if (a.read_likelihood.empty()) read_sample(a, r, groupings[0].indicators.size());
   } catch (const std::exception &ex) {
     std::cerr << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
     msw_core_destroy(h);

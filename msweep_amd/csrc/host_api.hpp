@@ -4,12 +4,16 @@
 // (and the file of text) that defines it.
 #pragma once
 #include "handle.hpp"
+#include "lds_grants.hpp"
 #include "prim_ops.hpp"
 
 namespace msw {
 namespace host __attribute__((visibility("hidden"))) {
 
 extern thread_local std::string g_create_error;  // msweep_core.hip: msw_last_error(null), msw_comm_last_error
+// msweep_core.hip: the dynamic-LDS limit of `kernel` on the current device becomes at least `bytes` (lds_grants.hpp: one
+// table for all handles, limits only rise)
+void grant_dynamic_lds(const void *kernel, size_t bytes);
 
 // ---- the sweeps, each beside the instantiations it launches --------------------------------------------------------
 // sweep_narrow.hip, sweep_wide.hip, sweep_index.hip (index and value records): k_passA and k_passB of an encoding

@@ -143,8 +143,8 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
   if (n_long && !hist_lds) scratch.alloc((size_t)nbl * G);
   const size_t lds_long = hist_lds ? G * sizeof(uint32_t) : 0;
   if (n_long && hist_lds) {
-    MSW_HIP(hipFuncSetAttribute((const void *)k_ec_groups_long<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
-    MSW_HIP(hipFuncSetAttribute((const void *)k_ec_groups_long<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_long));
+    grant_dynamic_lds((const void *)k_ec_groups_long<false>, lds_long);
+    grant_dynamic_lds((const void *)k_ec_groups_long<true>, lds_long);
   }
   if (n_mid)
     hipLaunchKernelGGL(k_ec_groups_wave<false>, dim3(nbw), dim3(256), 0, st, d_mid.p, n_mid, d_tptr, d_targets,
@@ -188,8 +188,7 @@ void build_likelihood_impl(msw_core *h, const uint64_t *ec_tptr, const uint32_t 
     h->in_collective = h->comm != nullptr;
     d_hits.alloc(G);
     MSW_HIP(hipMemsetAsync(d_hits.p, 0, G * sizeof(unsigned long long), st));
-    MSW_HIP(hipFuncSetAttribute((const void *)k_group_hits, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(kHitsGroups * sizeof(unsigned long long))));
+    grant_dynamic_lds((const void *)k_group_hits, kHitsGroups * sizeof(unsigned long long));
     for (uint32_t g0 = 0; g0 < G; g0 += kHitsGroups) {
       const uint32_t ng = (uint32_t)std::min<size_t>(kHitsGroups, G - g0);
       hipLaunchKernelGGL(k_group_hits, dim3((unsigned)std::min<size_t>((E + 1023) / 1024, (size_t)h->n_cu)), dim3(1024),

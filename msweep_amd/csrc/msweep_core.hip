@@ -9,6 +9,15 @@
 
 thread_local std::string msw::host::g_create_error;
 
+void msw::host::grant_dynamic_lds(const void *kernel, size_t bytes) {
+  static msw::LdsGrants grants;  // (the one process-wide table of the library besides the code objects themselves)
+  int device = 0;
+  MSW_HIP(hipGetDevice(&device));
+  grants.raise(device, kernel, bytes, [&](size_t b) {
+    MSW_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
+  });
+}
+
 // =========================================================================================
 // C ABI
 // =========================================================================================

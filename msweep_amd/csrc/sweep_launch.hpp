@@ -16,7 +16,7 @@ void prepare_sweep(K k, size_t lds, size_t &lds_set) {
     hipFuncAttributes fa;
     MSW_HIP(hipFuncGetAttributes(&fa, (const void *)k));
     if (fa.sharedSizeBytes != 0) throw Fail("internal: sweep kernel owns static LDS");
-    MSW_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    grant_dynamic_lds((const void *)k, lds);  // (process wide and only ever raised: another handle's smaller layout does not lower it)
     lds_set = lds;
   }
 }
