@@ -623,6 +623,41 @@ int msw_core_build_likelihood_aln(msw_handle h, msw_alignment_t a, const uint32_
                                   const uint64_t *group_sizes, size_t n_groups, double q, double e,
                                   double zero_inflation, size_t min_hits, size_t *n_groups_out, uint8_t *mask_out,
                                   double *logc_out);
+/* An alignment RESTRICTED to a set of reads and a set of target sequences, collapsed into equivalence classes again
+ * (msweep_amd/csrc/host_subset.inc, subset_kernels.hpp).  The whole contract:
+ *   *out is, array for array (ec_tptr, ec_targets, ec_counts, ec_rptr, ec_reads and the four numbers of
+ *   msw_alignment_shape), the alignment of the single-strand plaintext text with *n_targets_out = the number of non-zero
+ *   entries of keep_target[a's n_targets] target sequences that holds one line per entry of read_ids: the read id as it is
+ *   (ids are NOT renumbered), followed by those targets of the read's class in `a` that keep_target keeps, each written as
+ *   its rank among the kept targets (kept sequences are renumbered 0 .. n_keep - 1 in ascending order).  A read that is in
+ *   no class of `a`, or whose targets are all dropped, gives a bare id.
+ * Hence n_reads = n_ids; unaligned reads are dropped; classes stand in ascending order of the reference's 64-bit hash over
+ * the RENUMBERED ids, reads with equal hash share a class, a class's target list is that of its smallest read id, read ids
+ * ascend inside a class.  Classes of `a` that differed only in dropped targets fall together; a class of which no read is
+ * selected, or which loses every target, is gone.
+ * EVERY selected read takes part, whatever its id: this is the text as the reader's rule (and the pure-Python mirror,
+ * msweep_amd/alignment.py) reads it.  msw_alignment_read itself leaves out read ids at or beyond the text's LINE COUNT
+ * (its guard against a malformed line sizing the tables; a Themisto file numbers its reads 0 .. lines - 1), so on a text
+ * of n_ids lines it returns the same arrays exactly when every selected id is below n_ids, and otherwise when the text is
+ * given one bare line for every id that is not selected, up to the largest one (tests/test_alignment_subset_cpu.py).
+ * The output is an ordinary alignment handle: it can be built from, binned, assigned and subset again, and is freed by
+ * msw_alignment_destroy.  `a` is not modified.
+ * Refused (non-zero, msw_last_error(h); msw_last_error(NULL) when h is NULL): a read id listed twice (the message names
+ * the SMALLEST such id, whatever the order of read_ids and of the threads); keep_target all zero; `a` resident on another
+ * device than h's; a NULL h with a device-resident `a`.  n_ids == 0, and a selection in which no read keeps a target, are
+ * valid and give an alignment of 0 classes.
+ * A device-resident `a` is served by kernels on h's stream, its result stays resident: the kept targets are ranked by a
+ * scan, every class's list is filtered, renumbered and hashed ONCE, the selection becomes a bitmap over the read ids, the
+ * selected reads carry their class's hash through a stable radix sort, and the classes are taken as the reader takes them.
+ * No atomic decides an order: two calls give the same bytes.  Device memory: O(largest selected id + classes and hits of
+ * `a` + the output), temporaries from the handle's reader pool (msw_core_trim); an allocation that fails is an error that
+ * names the bytes, never a fall back.  A host-resident `a` (msw_alignment_read, or the host parser behind the device
+ * entry) is served by plain loops on the host, h may be NULL and no GPU is touched.
+ * MSWEEP_HOST_SUBSET=1 in the environment (developer switch, read at the call): the host loops also for a resident `a`.
+ * This restricts the pseudoalignment against the FULL index; it is not a pseudoalignment against an index of the kept
+ * sequences alone. */
+int msw_alignment_subset(msw_handle h, msw_alignment_t a, const uint32_t *read_ids, size_t n_ids, const uint8_t *keep_target,
+                         msw_alignment_t *out, size_t *n_targets_out);
 /* error text of the last failed msw_alignment_read of this thread (the reference's messages) */
 const char *msw_alignment_last_error(void);
 

@@ -15,7 +15,10 @@ Every tab-separated column of the -i file is a grouping of its own: the estimati
 (src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several.
 --samples FILE runs a whole manifest of samples (msweep_amd/samples.py) in this one process: -i is read once, every worker
 (--devices, one per entry) keeps one handle for its life and takes the next sample from a shared queue, and each sample's
-files are those a single run with its -o / --themisto / --extract-reads writes (run_samples below)."""
+files are those a single run with its -o / --themisto / --extract-reads writes (run_samples below).
+--nested makes the K >= 2 columns of -i ONE hierarchy, column 0 the coarsest: every node of the tree runs the per-grouping
+body, and every bin of a node is estimated within its group from a sub-alignment made on the device
+(Core.subset_alignment; run_nested below, msweep_amd/nested.py); files `<prefix>_<stem>_...`."""
 import argparse
 import copy
 import math
@@ -25,10 +28,10 @@ import threading
 
 import numpy as np
 
-from . import binning, parallel, samples
+from . import binning, nested, parallel, samples
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
 from .likelihood import from_device_alignment, from_likelihood_file, read_likelihood_file  # noqa: F401 (read_likelihood_file: the host parser, under its name here)
-from .reference import output_path, read_references
+from .reference import Grouping, _split, output_path, read_references
 from .sample import BootstrapSample, PlainSample
 
 
@@ -75,6 +78,9 @@ def parse(argv):
     ap.add_argument("--samples", help="a manifest, one sample per line: <prefix> TAB <alignment files> [TAB <FASTQ files>]; "
                                       "takes the place of -o / --themisto / --extract-reads")
     ap.add_argument("--devices", help="with --samples: d0[,d1,...], one worker per entry (an entry may repeat)")
+    ap.add_argument("--nested", action="store_true",
+                    help="the K >= 2 columns of -i are one hierarchy, column 0 the coarsest: every bin of a node is estimated "
+                         "within its group from a sub-alignment made on the device (files <prefix>_<stem>_...)")
     ap.add_argument("--verbose", action="store_true")
     return ap.parse_args(argv)
 
@@ -289,7 +295,7 @@ def dirichlet_kld_rate(alphas):
 EXTRACT_PIECE = 256 << 20     # bytes of records per Fastq.pieces call
 
 
-def extract_reads(core, aln, targets, bin_ptr, reads, a):
+def extract_reads(core, aln, targets, bin_ptr, reads, a, n_reads=None):
     """--extract-reads: for the k-th FASTQ file (from 1) and every target group g, `<dir>/<g>_<k>.fastq` (`.fastq.gz`, one
     gzip stream, under --compress z) holds the records whose 0-based number in the file is a read id of g's bin, verbatim
     and in file order; an empty bin gives an empty file.  The files are opened at the first grouping that bins, stay
@@ -309,9 +315,10 @@ def extract_reads(core, aln, targets, bin_ptr, reads, a):
                     else:
                         _say(a, f"note: {path}: plain text; {fq.info['n_records']} records\n")
         # before any file is written: a read file of another sample has another number of records
+        n_reads = aln.n_reads if n_reads is None else n_reads      # (--nested: a child's bins hold the root's read ids)
         for path, fq in zip(a.extract_reads, a.fastqs):
-            if fq.info["n_records"] != aln.n_reads:
-                raise RuntimeError(f"{path} holds {fq.info['n_records']} records, the pseudoalignment {aln.n_reads} reads")
+            if fq.info["n_records"] != n_reads:
+                raise RuntimeError(f"{path} holds {fq.info['n_records']} records, the pseudoalignment {n_reads} reads")
         for k_file, fq in enumerate(a.fastqs, 1):
             for k, name in enumerate(targets):
                 fq.select(reads[int(bin_ptr[k]):int(bin_ptr[k + 1])])
@@ -343,14 +350,16 @@ def write_assignment_table(core, path, targets, a):
                 f.write(core.assign_table_block(r0, r1))
 
 
-def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
+def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note="", node=None):
     """--bin-reads (src/mSWEEP.cpp:437-469): targets, thresholds 1 - theta, the bins from the device, one file per
     target (an empty bin gives an empty file), then --extract-reads.  With --write-unassigned / --write-assignment-table
     the bins come from Core.assign_reads_aln, which judges every class against all estimated groups: one more bin for the
-    reads nobody claims, and the table.  Returns the exit status."""
+    reads nobody claims, and the table.  Under --nested (`node`: the node of the walk) the bins are taken whether or not
+    --bin-reads is given and stay on the node for the descent; below the root --min-abundance alone chooses the groups
+    (--target-groups names level-0 groups) and the files are `<dir>/<stem>_<group>.bin`.  Returns the exit status."""
     extras = a.write_unassigned or a.write_assignment_table
     try:
-        targets = binning.resolve_targets(estimated_names, a.target_groups)
+        targets = binning.resolve_targets(estimated_names, a.target_groups if node is None or node.depth == 0 else None)
         if a.min_abundance is not None:
             targets = binning.filter_min_abundance(targets, estimated_names, theta, a.min_abundance)
         row = {n: i for i, n in enumerate(estimated_names)}
@@ -371,6 +380,11 @@ def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
         _say(a, f"Binning the reads failed:\n  {ex}\nexiting\n")
         return 1
     bins = list(targets) + ([binning.UNASSIGNED] if a.write_unassigned else [])    # the unassigned bin is the last one
+    if node is not None:
+        node.bins = (list(targets), rows, bin_ptr, reads)
+        if not a.bin_reads:
+            return 0
+        bins = [nested.bin_name(node.stem, t) for t in targets]
     for k, name in enumerate(bins):
         try:
             ids = reads[int(bin_ptr[k]):int(bin_ptr[k + 1])]
@@ -389,8 +403,76 @@ def bin_reads(core, aln, estimated_names, theta, a, table_path=None, note=""):
             _say(a, f"Writing the assignment table failed:\n  {ex}\nexiting\n")
             return 1
     if a.extract_reads:
-        return extract_reads(core, aln, bins, bin_ptr, reads, a)
+        return extract_reads(core, aln, bins, bin_ptr, reads, a, None if node is None else node.root_reads)
     return 0
+
+
+class Node:
+    """a node of the --nested walk: its group names, and after its run the bins the descent takes"""
+
+    def __init__(self, names, root_reads, descend):
+        self.names, self.depth, self.stem = list(names), len(names), nested.stem(names)
+        self.root_reads, self.descend, self.bins = root_reads, descend, None
+
+
+def read_indicator_rows(a):
+    """--nested: the fields of every line of -i (read_references has judged the file)"""
+    with open(a.indicators) as f:
+        read_references(f)
+    with open(a.indicators) as f:
+        return [_split(ln.rstrip("\n"), "\t") for ln in f]
+
+
+def run_nested(a, core, aln, algo, prec):
+    """--nested: the columns of -i as one tree, walked depth-first on the one handle.  A node runs the per-grouping body
+    (run_grouping) on its alignment and the column of its depth; below depth K - 1 it then takes, for every binned group g
+    in group order, the subset of its alignment with g's bin and the sequences labelled g (Core.subset_alignment: made on
+    the device), forms the child grouping from the next column on exactly those -i lines, runs the child
+    and closes the child's alignment.  A child without a class, or whose sequences carry fewer than two groups in the next
+    column, is skipped (--verbose says why).  A child that fails ends the run: its message carries `node <stem>: `."""
+    rows = a.nested_rows
+    K = len(rows[0])
+
+    def walk(node_aln, lines, names):
+        depth = len(names)
+        grouping = Grouping([rows[i][depth] for i in lines])
+        node = Node(names, aln.n_reads, depth < K - 1)
+        na = a
+        if names:
+            na = copy.copy(a)
+            na.sample_tag = getattr(a, "sample_tag", "") + f"node {node.stem}: "
+        rc = run_grouping(na, core, node_aln, grouping, 0, 1, algo, prec, node)
+        if rc or not node.descend:
+            return rc
+        targets, trows, bin_ptr, reads = node.bins
+        order = sorted(range(len(targets)), key=lambda k: grouping.name_to_id[targets[k]])      # group order
+        labels = np.array([rows[i][depth] for i in lines], dtype=object)
+        for k in order:
+            g = targets[k]
+            child = list(names) + [g]
+            keep = labels == g
+            child_lines = [i for i, kp in zip(lines, keep) if kp]
+            if len({rows[i][depth + 1] for i in child_lines}) < 2:
+                if a.verbose:
+                    _say(a, f"note: node {nested.stem(child)}: skipped, its sequences carry fewer than two groups in column {depth + 1}\n")
+                continue
+            try:
+                sub = core.subset_alignment(node_aln, reads[int(bin_ptr[k]):int(bin_ptr[k + 1])], keep.astype(np.uint8))
+            except MswError as ex:
+                _say(a, f"node {nested.stem(child)}: Restricting the pseudoalignment failed:\n  {ex}\nexiting\n")
+                return 1
+            try:
+                if sub.n_ecs == 0:
+                    if a.verbose:
+                        _say(a, f"note: node {nested.stem(child)}: skipped, no read of its bin aligns against its sequences\n")
+                    continue
+                rc = walk(sub, child_lines, child)
+                if rc:
+                    return rc
+            finally:
+                sub.close()
+        return 0
+    return walk(aln, list(range(len(rows))), [])
 
 
 def read_indicators(a):
@@ -426,6 +508,8 @@ def run_groupings(a, core, aln, groupings, algo, prec):
     build replaces the resident likelihood and all that was derived from the one before (include/msweep_core.h).  A
     grouping that fails ends the sample; the files of the groupings before it stay.  Returns the exit status."""
     try:
+        if a.nested:
+            return run_nested(a, core, aln, algo, prec)      # the walk takes the place of the loop
         for index, grouping in enumerate(groupings):
             rc = run_grouping(a, core, aln, grouping, index, len(groupings), algo, prec)
             if rc:
@@ -569,6 +653,22 @@ def main(argv=None):
         if any(not p for p in a.extract_reads):
             sys.stderr.write("Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n")
             return 1
+    if a.nested:
+        # --nested: the flags it refuses and the tree of -i are judged before the GPU is touched (msweep_amd/nested.py)
+        given = [f for f, v in (("--read-likelihood", a.read_likelihood), ("--no-fit-model", a.no_fit_model), ("--alphas", a.alphas),
+                                ("--write-unassigned", a.write_unassigned), ("--write-assignment-table", a.write_assignment_table),
+                                ("--print-probs", a.print_probs)) if v]
+        try:
+            nested.check_flags(given)
+            try:
+                a.nested_rows = read_indicator_rows(a)
+            except (RuntimeError, OSError) as ex:
+                sys.stderr.write(f"Reading the pseudoalignments failed:\n  {ex}\nexiting\n")
+                return 1
+            nested.check_tree(a.indicators, a.nested_rows)
+        except nested.NestedError as ex:
+            sys.stderr.write(f"Parsing arguments failed:\n  {ex}\nexiting\n")
+            return 1
     if manifest is not None:
         return run_samples(a, manifest, devices)
     a.fastqs = []     # the read files of --extract-reads, resident from the first grouping that bins
@@ -618,10 +718,12 @@ def main(argv=None):
     return 0
 
 
-def run_grouping(a, core, aln, grouping, index, K, algo, prec):
+def run_grouping(a, core, aln, grouping, index, K, algo, prec, node=None):
     """Everything main() does per grouping column: the body of the loop at src/mSWEEP.cpp:282-563.  Returns the exit
-    status (0: go on with the next grouping)."""
-    def path(name):      # <prefix>_<name>, <prefix>_<index>_<name> when -i has several columns
+    status (0: go on with the next grouping).  node: the node of the --nested walk this run is (run_nested)."""
+    def path(name):      # <prefix>_<name>, <prefix>_<index>_<name> when -i has several columns; --nested: <prefix>_<stem>_<name>
+        if node is not None:
+            return nested.node_path(a.prefix, node.stem, name)
         return output_path(a.prefix, index, K, name)
     note = f"grouping {index}: " if K > 1 else ""     # --verbose: in front of the notes of a grouping
     try:
@@ -680,10 +782,10 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec):
     except MswError as ex:
         _say(a, f"Estimating relative abundances failed:\n  {ex}\nexiting\n")
         return 1
-    if a.bin_reads:
+    if a.bin_reads or (node is not None and node.descend):
         # before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
         est = [n for n, m in zip(grouping.get_names(), lik.groups_considered()) if m]
-        rc = bin_reads(core, aln, est, res["theta"], a, path("reads_to_groups.tsv"), note)
+        rc = bin_reads(core, aln, est, res["theta"], a, path("reads_to_groups.tsv"), note, node)
         if rc:
             return rc
     try:

@@ -42,7 +42,7 @@ EXPORTS = [
     "msw_core_assign_table_block_gzip",
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
-    "msw_core_inflate_gzip", "msw_alignment_last_inflate",
+    "msw_core_inflate_gzip", "msw_alignment_last_inflate", "msw_alignment_subset",
     "msw_core_set_dense_logl_file", "msw_core_set_dense_logl_text", "msw_core_likfile_counts",
     "msw_fastq_open", "msw_fastq_select", "msw_fastq_next", "msw_fastq_next_gzip", "msw_fastq_last_timing", "msw_fastq_close",
 ]
@@ -237,6 +237,7 @@ def load_library():
     L.msw_alignment_read_device.argtypes = [vp, C.POINTER(C.c_char_p), sz, sz, C.c_int, C.POINTER(vp)]
     L.msw_core_build_likelihood_aln.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, C.c_double, C.c_double, sz,
                                                 C.POINTER(sz), vp, vp]
+    L.msw_alignment_subset.argtypes = [vp, vp, vp, sz, vp, C.POINTER(vp), C.POINTER(sz)]
     L.msw_alignment_destroy.restype = None
     L.msw_alignment_last_error.restype = C.c_char_p
     _lib = L
@@ -283,6 +284,44 @@ def read_alignment(paths, n_targets, merge_mode="intersection", copy=False):
             raise MswError("msw_alignment_export failed")
         return out
     return _alignment_views(L, h, owner, ne.value, nh.value, na.value, nr.value)
+
+
+def read_alignment_handle(paths, n_targets, merge_mode="intersection"):
+    """read_alignment() as a handle (a DeviceAlignment whose arrays are host-resident: on_device is False): what
+    subset_alignment() takes and returns.  No GPU is touched."""
+    L = load_library()
+    if merge_mode not in ("intersection", "union"):
+        raise MswError(f"Unrecognized option `{merge_mode}` for --themisto-mode")
+    arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+    h = C.c_void_p()
+    if L.msw_alignment_read(arr, len(paths), int(n_targets), 0 if merge_mode == "intersection" else 1, C.byref(h)):
+        raise MswError(L.msw_alignment_last_error().decode())
+    a = DeviceAlignment(L, h)
+    a.n_targets = int(n_targets)
+    return a
+
+
+def _subset(L, core_h, aln, read_ids, keep):
+    read_ids = _arr(read_ids, np.uint32)
+    keep = _arr(np.asarray(keep) != 0, np.uint8)
+    n_targets = getattr(aln, "n_targets", None)
+    if n_targets is not None and len(keep) != n_targets:
+        raise MswError(f"subset_alignment: keep has {len(keep)} entries, the alignment {n_targets} target sequences")
+    h, nt = C.c_void_p(), C.c_size_t()
+    if L.msw_alignment_subset(core_h, aln._h, _ptr(read_ids) if len(read_ids) else None, len(read_ids), _ptr(keep),
+                              C.byref(h), C.byref(nt)):
+        raise MswError(L.msw_last_error(core_h).decode())
+    out = DeviceAlignment(L, h)
+    out.n_targets = int(nt.value)
+    return out
+
+
+def subset_alignment(aln, read_ids, keep):
+    """msw_alignment_subset without a handle, for a HOST-resident alignment (read_alignment_handle, or a Core.read_alignment
+    the host parser served): the alignment restricted to the reads `read_ids` and the target sequences with keep[t] != 0,
+    collapsed into classes again -- kept targets renumbered by rank, read ids as they are (include/msweep_core.h states
+    the contract).  Returns a handle like `aln` with .n_targets = the number of kept sequences.  No GPU is touched."""
+    return _subset(load_library(), None, aln, read_ids, keep)
 
 
 class DeviceAlignment:
@@ -526,7 +565,16 @@ class Core:
         if self._L.msw_alignment_read_device(self._h, arr, len(paths), int(n_targets),
                                              0 if merge_mode == "intersection" else 1, C.byref(h)):
             raise MswError(self._L.msw_alignment_last_error().decode())
-        return DeviceAlignment(self._L, h)
+        a = DeviceAlignment(self._L, h)
+        a.n_targets = int(n_targets)
+        return a
+
+    def subset_alignment(self, aln, read_ids, keep):
+        """msw_alignment_subset on this GPU: `aln` restricted to the reads `read_ids` and the target sequences with
+        keep[t] != 0, collapsed into classes again by kernels; the result stays resident (a DeviceAlignment with
+        .n_targets = the number of kept sequences: it can be built from, binned, assigned and subset again).  A
+        host-resident `aln` is served by the host loops (the module's subset_alignment)."""
+        return _subset(self._L, self._h, aln, read_ids, keep)
 
     def trim(self):
         """Gives the device temporaries of read_alignment back (kept on the handle between calls: msw_core_trim)."""

@@ -24,6 +24,9 @@
 // --samples FILE runs a whole manifest of samples (samples_manifest.hpp) in this one process: -i is read once, every worker
 // (--devices, one std::thread per entry) keeps one handle for its life and takes the next sample from a shared queue, and
 // each sample's files are those a single run with its -o / --themisto / --extract-reads writes (run_samples).
+// --nested makes the K >= 2 columns of -i ONE hierarchy, column 0 the coarsest: every node of the tree runs run_grouping(),
+// and every bin of a node is estimated within its group from a sub-alignment made on the device (msw_alignment_subset;
+// run_nested_node, nested_tree.hpp); files `<prefix>_<stem>_...` (tests/test_gpu_cli_nested.py).
 //
 //   g++ -std=c++17 -O2 -o msweep_mini msweep_mini.cpp -L.. -lmsweep_core -Wl,-rpath,..
 #include <algorithm>
@@ -47,6 +50,7 @@
 #include <vector>
 
 #include "../../include/msweep_core.h"
+#include "nested_tree.hpp"
 #include "samples_manifest.hpp"
 
 namespace {
@@ -75,6 +79,10 @@ struct Args {
   bool have_samples = false, have_devices = false;
   std::string samples, devices;
   std::vector<std::string> given;  // the flags of msw_samples::conflicts() that the command line holds
+  // --nested: the columns of -i are one hierarchy; the fields of its lines, and the flags of msw_nested::conflicts() given
+  bool nested = false;
+  std::vector<std::vector<std::string>> nested_rows;
+  std::vector<std::string> nested_given;
 };
 
 // A message of the run to stderr, written whole when the object goes: under --samples the lines of two workers do not mix,
@@ -116,6 +124,8 @@ Args parse(int argc, char **argv) {
     };
     for (const std::string &f : msw_samples::conflicts())
       if (k == f) a.given.push_back(k);
+    for (const std::string &f : msw_nested::conflicts())
+      if (k == f) a.nested_given.push_back(k);
     if (k == "--themisto") a.themisto = split(val(), ',');
     else if (k == "--themisto-1") t1 = val();
     else if (k == "--themisto-2") t2 = val();
@@ -137,6 +147,7 @@ Args parse(int argc, char **argv) {
     else if (k == "--gpu-index") a.gpu = std::stoi(val());
     else if (k == "-t") (void)val();  // host threads: nothing to set here
     else if (k == "--verbose") a.verbose = true;
+    else if (k == "--nested") a.nested = true;
     else if (k == "--write-probs") a.write_probs = true;
     else if (k == "--print-probs") a.print_probs = true;
     else if (k == "--write-likelihood") a.write_likelihood = true;
@@ -195,7 +206,24 @@ struct Grouping {
   std::vector<uint64_t> sizes;
   std::vector<uint32_t> indicators;
 };
-std::vector<Grouping> read_groupings(const std::string &path) {
+// the grouping a single-column file of these labels gives
+Grouping grouping_of(const std::vector<std::string> &labels) {
+  Grouping g;
+  std::unordered_map<std::string, uint32_t> ids;
+  for (const std::string &l : labels) {
+    auto it = ids.find(l);
+    if (it == ids.end()) {
+      it = ids.emplace(l, (uint32_t)g.names.size()).first;
+      g.names.push_back(l);
+      g.sizes.push_back(0);
+    }
+    ++g.sizes[it->second];
+    g.indicators.push_back(it->second);
+  }
+  return g;
+}
+// rows: when given, the fields of every line (--nested)
+std::vector<Grouping> read_groupings(const std::string &path, std::vector<std::vector<std::string>> *rows = nullptr) {
   std::ifstream in(path);
   if (!in) throw std::runtime_error("cannot open " + path);
   std::vector<Grouping> gs;
@@ -213,6 +241,7 @@ std::vector<Grouping> read_groupings(const std::string &path) {
     if (fields.size() != gs.size())
       throw std::runtime_error("The grouping has " + std::to_string(fields.size()) + " columns on line " + std::to_string(n_lines) +
                                ", " + std::to_string(gs.size()) + " on line 1");
+    if (rows) rows->push_back(fields);
     for (size_t c = 0; c < gs.size(); ++c) {
       Grouping &g = gs[c];
       auto it = ids[c].find(fields[c]);
@@ -381,6 +410,18 @@ struct Run {
   // --extract-reads: the read files, opened at the first grouping that bins, and their record counts
   mutable std::vector<msw_fastq_t> fastqs;
   mutable std::vector<uint64_t> fastq_records;
+  const Run *root = nullptr;  // --nested, below the root: the run that holds the read files and the sample's read count
+};
+
+// a node of the --nested walk: its stem and depth, and after its run the bins the descent takes
+struct Node {
+  std::string stem;
+  size_t depth = 0;
+  bool descend = false;
+  std::vector<std::string> targets;
+  std::vector<uint32_t> rows;
+  std::vector<uint64_t> bin_ptr;
+  std::vector<uint32_t> reads;
 };
 
 // ---- --bin-reads (src/mSWEEP.cpp:437-469; the same choices as msweep_amd/binning.py) ---------------------------------
@@ -392,11 +433,11 @@ struct BinningError : std::runtime_error {
 // name that is not an estimated group (unknown, or pruned by --min-hits) is refused.  --min-abundance m drops a
 // target with theta < m (mGEMS::FilterTargetGroups), ties kept.  Returns the rows of the kept groups.
 std::vector<uint32_t> bin_targets(const Args &a, const std::vector<std::string> &est, const std::vector<double> &theta,
-                                  std::vector<std::string> &names) {
+                                  std::vector<std::string> &names, bool use_target_groups = true) {
   std::unordered_map<std::string, uint32_t> row;
   for (size_t i = 0; i < est.size(); ++i) row.emplace(est[i], (uint32_t)i);
   names.clear();
-  for (const std::string &n : a.have_target_groups ? a.target_groups : est) {
+  for (const std::string &n : a.have_target_groups && use_target_groups ? a.target_groups : est) {
     if (!row.count(n)) throw BinningError("target group " + n + " is not among the estimated groups");
     if (std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n);
   }
@@ -510,7 +551,8 @@ int extract_reads(const Args &a, msw_handle h, size_t n_reads, std::vector<msw_f
 int extract_after_bins(const Args &a, msw_handle h, const Run &r, const std::vector<std::string> &names,
                        const std::vector<uint64_t> &bin_ptr, const std::vector<uint32_t> &reads) {
   if (!a.have_extract_reads) return 0;
-  return extract_reads(a, h, r.n_reads, r.fastqs, r.fastq_records, names, bin_ptr, reads);
+  const Run &top = r.root ? *r.root : r;  // (--nested: a child's bins hold the root's read ids)
+  return extract_reads(a, h, top.n_reads, top.fastqs, top.fastq_records, names, bin_ptr, reads);
 }
 
 // --write-assignment-table: `#read_id` and the target names, then the rows of the table the device kept, a block of
@@ -532,16 +574,20 @@ void write_assignment_table(const Args &a, msw_handle h, const std::string &path
 // the bins from the device and one file per target (an empty bin: an empty file), written on up to writer_threads()
 // threads, then --extract-reads; with --write-unassigned / --write-assignment-table the bins come from
 // msw_core_assign_reads_aln, which judges every class against all estimated groups: one more bin, <dir>/unassigned_reads.bin,
-// and the table.  Returns the exit status.
+// and the table.  Under --nested (`node`: the node of the walk) the bins are taken whether or not --bin-reads is given and
+// stay on the node for the descent; below the root --min-abundance alone chooses the groups (--target-groups names level-0
+// groups) and the files are `<dir>/<stem>_<group>.bin`.  Returns the exit status.
 int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vector<std::string> &est,
-              const std::vector<double> &theta, const Run &r, const std::string &table_path, const std::string &note) {
+              const std::vector<double> &theta, const Run &r, const std::string &table_path, const std::string &note,
+              Node *node = nullptr) {
   std::vector<std::string> names, targets;
   std::vector<uint64_t> bin_ptr;
   std::vector<uint32_t> reads;
   const bool extras = a.write_unassigned || a.write_assignment_table;
   try {
-    const std::vector<uint32_t> rows = bin_targets(a, est, theta, names);
+    const std::vector<uint32_t> rows = bin_targets(a, est, theta, names, !node || node->depth == 0);
     targets = names;
+    if (node) node->rows = rows;
     if (extras) {
       if (a.write_unassigned && std::find(est.begin(), est.end(), "unassigned_reads") != est.end())
         throw BinningError("a group is named unassigned_reads, the name of the file --write-unassigned writes");
@@ -570,6 +616,13 @@ int bin_reads(const Args &a, msw_handle h, msw_alignment_t aln, const std::vecto
   } catch (const std::exception &ex) {
     Msg() << "Binning the reads failed:\n  " << ex.what() << "\nexiting\n";
     return 1;
+  }
+  if (node) {
+    node->targets = targets;
+    node->bin_ptr = bin_ptr;
+    node->reads = reads;
+    if (!a.bin_reads) return 0;
+    for (std::string &nm : names) nm = msw_nested::bin_name(node->stem, nm);
   }
   const size_t n = names.size(), nt = std::min(n, writer_threads());
   std::vector<std::string> err(n);
@@ -782,9 +835,14 @@ void dirichlet_kld_rate(const std::vector<double> &alphas, std::vector<double> &
 // this column's indicators (it replaces the resident likelihood and all that was derived from the one before,
 // include/msweep_core.h), the likelihood outputs, the solve, the bins, the bootstrap, the probabilities and the
 // abundances.  Returns the exit status (0: go on with the next grouping).
-int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t index) {
+// node: the node of the --nested walk this run is (run_nested)
+int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t index, Node *node = nullptr) {
   msw_handle h = r.h;
-  const size_t K = r.n_groupings;
+  const size_t K = node ? 1 : r.n_groupings;
+  // <prefix>_<name>, <prefix>_<index>_<name> when -i has several columns; --nested: <prefix>_<stem>_<name>
+  auto path = [&](const std::string &name) {
+    return node ? msw_nested::node_path(a.prefix, node->stem, name) : out_path(a.prefix, index, K, name);
+  };
   const std::string note = K > 1 ? "grouping " + std::to_string(index) + ": " : std::string();  // --verbose
   const size_t G = grouping.names.size();
   size_t n_ecs = r.n_ecs, n_reads = r.n_reads, n_kept = 0;
@@ -837,11 +895,11 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
     // written here if requested (src/mSWEEP.cpp:373-380: a failure has a message of its own)
     if (a.write_likelihood_bitseq) {
       // both likelihood flags: only the BitSeq file (src/mSWEEP.cpp:375-376)
-      Out lf(h, out_path(a.prefix, index, K, "bitseq_likelihoods.tsv"), a.compress == "z", a.compression_level);
+      Out lf(h, path("bitseq_likelihoods.tsv"), a.compress == "z", a.compression_level);
       write_likelihood_bitseq(lf, h, ec_counts, n_kept, n_ecs);
     } else if (a.write_likelihood) {
       // --write-likelihood (include/Likelihood.hpp:255-273; the file: src/OutfileDesignator.cpp:67-74)
-      Out lf(h, out_path(a.prefix, index, K, "likelihoods.tsv"), a.compress == "z", a.compression_level);
+      Out lf(h, path("likelihoods.tsv"), a.compress == "z", a.compression_level);
       write_likelihood(lf, h, ec_counts, n_kept, n_ecs);
     }
   } catch (const std::exception &ex) {
@@ -883,9 +941,9 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       }
     }
     results.push_back(theta);
-    if (a.bin_reads) {
+    if (a.bin_reads || (node && node->descend)) {
       // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
-      if (bin_reads(a, h, r.aln, est_names, theta, r, out_path(a.prefix, index, K, "reads_to_groups.tsv"), note) != 0) return 1;
+      if (bin_reads(a, h, r.aln, est_names, theta, r, path("reads_to_groups.tsv"), note, node) != 0) return 1;
     }
     if (a.iters > 0) {
       // every grouping's bootstrap starts the stream from the same seed (the reference constructs the sample inside its
@@ -913,7 +971,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       const std::vector<std::string> none;
       const std::vector<std::string> &zn = a.min_hits > 0 ? zero_names : none;
       if (a.write_probs && !a.prefix.empty()) {
-        Out pf(h, out_path(a.prefix, index, K, "probs.tsv"), a.compress == "z", a.compression_level);
+        Out pf(h, path("probs.tsv"), a.compress == "z", a.compression_level);
         write_probs(pf, h, est_names, zn, n_kept, n_ecs);
       }
       if (a.print_probs || (a.write_probs && a.prefix.empty())) {
@@ -928,7 +986,7 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
 
   // ---- abundances (default ostream formatting = 6 significant digits, as the reference) ----------
   std::ofstream file;
-  if (!a.prefix.empty()) file.open(out_path(a.prefix, index, K, "abundances.txt"));
+  if (!a.prefix.empty()) file.open(path("abundances.txt"));
   std::ostream &of = a.prefix.empty() ? std::cout : file;
   of << "#mSWEEP_version:\t" << kVersion << '\n' << "#num_reads:\t" << n_reads << '\n' << "#num_aligned:\t" << total << '\n';
   if (a.run_rate) {
@@ -998,6 +1056,94 @@ void read_sample(const Args &a, Run &r, size_t n_targets) {
   msw_alignment_export(r.aln, nullptr, nullptr, r.ec_counts.data(), nullptr, nullptr);
 }
 
+// --nested: the columns of -i as one tree, walked depth-first on the one handle.  A node runs the per-grouping body
+// (run_grouping) on its alignment and the column of its depth; below depth K - 1 it then takes, for every binned group g in
+// group order, the subset of its alignment with g's bin and the sequences labelled g (msw_alignment_subset: made on the
+// device), forms the child grouping from the next column on exactly those -i lines, runs the child and
+// destroys the child's alignment.  A child without a class, or whose sequences carry fewer than two groups in the next
+// column, is skipped (--verbose says why).  A child that fails ends the run: its message carries `node <stem>: `.  The same
+// steps as msweep_amd/__main__.py run_nested.
+int run_nested_node(const Args &a, const Run &r, const Run &root, const std::vector<size_t> &lines, const std::vector<std::string> &names) {
+  const auto &rows = a.nested_rows;
+  const size_t K = rows[0].size(), depth = names.size();
+  std::vector<std::string> labels;
+  for (size_t i : lines) labels.push_back(rows[i][depth]);
+  const Grouping grouping = grouping_of(labels);
+  Node node;
+  node.stem = msw_nested::stem(names);
+  node.depth = depth;
+  node.descend = depth + 1 < K;
+  const std::string tag = t_tag;
+  if (depth) t_tag += "node " + node.stem + ": ";
+  const int rc = run_grouping(a, r, grouping, 0, &node);
+  t_tag = tag;
+  if (rc != 0 || !node.descend) return rc;
+  std::vector<size_t> order(node.targets.size());
+  for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+  std::vector<uint32_t> gid(order.size());
+  for (size_t k = 0; k < order.size(); ++k)
+    gid[k] = (uint32_t)(std::find(grouping.names.begin(), grouping.names.end(), node.targets[k]) - grouping.names.begin());
+  std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return gid[x] < gid[y]; });  // group order
+  for (size_t k : order) {
+    const std::string &g = node.targets[k];
+    std::vector<std::string> child = names;
+    child.push_back(g);
+    std::vector<uint8_t> keep(lines.size(), 0);
+    std::vector<size_t> child_lines;
+    std::vector<std::string> next;
+    for (size_t j = 0; j < lines.size(); ++j)
+      if (labels[j] == g) {
+        keep[j] = 1;
+        child_lines.push_back(lines[j]);
+        if (std::find(next.begin(), next.end(), rows[lines[j]][depth + 1]) == next.end()) next.push_back(rows[lines[j]][depth + 1]);
+      }
+    if (next.size() < 2) {
+      if (a.verbose)
+        Msg() << "note: node " << msw_nested::stem(child) << ": skipped, its sequences carry fewer than two groups in column " << depth + 1
+              << "\n";
+      continue;
+    }
+    Run cr;
+    cr.h = r.h;
+    cr.n_groupings = 1;
+    cr.algo = r.algo;
+    cr.prec = r.prec;
+    cr.root = &root;
+    size_t n_keep = 0;
+    if (msw_alignment_subset(r.h, r.aln, node.reads.data() + node.bin_ptr[k], node.bin_ptr[k + 1] - node.bin_ptr[k], keep.data(), &cr.aln,
+                             &n_keep) != 0) {
+      Msg() << "node " << msw_nested::stem(child) << ": Restricting the pseudoalignment failed:\n  " << msw_last_error(r.h) << "\nexiting\n";
+      return 1;
+    }
+    size_t n_hits = 0, n_aligned = 0;
+    msw_alignment_shape(cr.aln, &cr.n_ecs, &cr.n_reads, &n_hits, &n_aligned);
+    int crc = 0;
+    if (cr.n_ecs == 0) {
+      if (a.verbose) Msg() << "note: node " << msw_nested::stem(child) << ": skipped, no read of its bin aligns against its sequences\n";
+    } else {
+      cr.ec_counts.resize(cr.n_ecs);
+      msw_alignment_export(cr.aln, nullptr, nullptr, cr.ec_counts.data(), nullptr, nullptr);
+      crc = run_nested_node(a, cr, root, child_lines, child);
+    }
+    msw_alignment_destroy(cr.aln);
+    if (crc != 0) return crc;
+  }
+  return 0;
+}
+
+// the grouping loop, or under --nested the walk that takes its place: a grouping that fails ends the run, the files of the
+// groupings before it stay
+int run_all(const Args &a, const Run &r, const std::vector<Grouping> &groupings) {
+  if (a.nested) {
+    std::vector<size_t> lines(a.nested_rows.size());
+    for (size_t i = 0; i < lines.size(); ++i) lines[i] = i;
+    return run_nested_node(a, r, r, lines, {});
+  }
+  int rc = 0;
+  for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(a, r, groupings[i], i);
+  return rc;
+}
+
 // Workers of --samples without --devices.  One: a second worker on the same device did not beat one by more than the
 // spread of the repeats at both measured shapes (profiles/batch_timing.txt).
 constexpr size_t kDefaultWorkers = 1;
@@ -1059,7 +1205,7 @@ int run_samples(const Args &a, const std::vector<msw_samples::Sample> &manifest,
         Msg() << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
         rc = 1;
       }
-      for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(sa, r, groupings[i], i);
+      if (rc == 0) rc = run_all(sa, r, groupings);
     } catch (const std::exception &ex) {  // what a single run would end on uncaught: this sample's failure
       Msg() << "Running the sample failed:\n  " << ex.what() << "\nexiting\n";
       rc = 1;
@@ -1148,6 +1294,22 @@ int main(int argc, char **argv) {
         return 1;
       }
   }
+  if (a.nested) {
+    // --nested: the flags it refuses and the tree of -i are judged before the GPU is touched (nested_tree.hpp)
+    try {
+      msw_nested::check_flags(a.nested_given);
+      try {
+        read_groupings(a.indicators, &a.nested_rows);
+      } catch (const std::exception &ex) {
+        std::cerr << "Reading the pseudoalignments failed:\n  " << ex.what() << "\nexiting\n";
+        return 1;
+      }
+      msw_nested::check_tree(a.indicators, a.nested_rows);
+    } catch (const msw_nested::NestedError &ex) {
+      std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
+      return 1;
+    }
+  }
   if (a.have_samples) return run_samples(a, manifest, devices);
   // every tab-separated column of -i is a grouping of its own; the estimation runs once per column
   // (src/mSWEEP.cpp:282), here from ONE resident alignment
@@ -1197,8 +1359,7 @@ int main(int argc, char **argv) {
     std::cerr << "Building the log-likelihood array failed:\n  " << msw_last_error(h) << "\nexiting\n";
     rc = 1;
   }
-  // the grouping loop: a grouping that fails ends the run, the files of the groupings before it stay
-  for (size_t i = 0; i < groupings.size() && rc == 0; ++i) rc = run_grouping(a, r, groupings[i], i);
+  if (rc == 0) rc = run_all(a, r, groupings);
   // (the pseudoalignment goes at the end: device memory given back is scrubbed before it is handed out again, and the
   // solver state is allocated after the build)
   for (msw_fastq_t fq : r.fastqs) msw_fastq_close(fq);

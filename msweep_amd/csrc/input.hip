@@ -1,8 +1,10 @@
-// input.hip -- translation unit of the input readers: the Themisto reader on the host and on the device, gzip / BGZF inflation,
+// input.hip -- translation unit of the input readers: the Themisto reader on the host and on the device, the subset of a
+// resident alignment (msw_alignment_subset), gzip / BGZF inflation,
 // --read-likelihood files and the FASTQ reader, with their C ABI entries.
 #include "host_api.hpp"
 
 #include "reader_kernels.hpp"
+#include "subset_kernels.hpp"
 #include "inflate_kernels.hpp"
 #include "inflate_member_kernels.hpp"
 #include "likelihood_text_kernels.hpp"
@@ -17,6 +19,7 @@ void msw::host::lik_gather_launch(hipStream_t st, const double *src, const uint6
 
 #include "host_alignment.inc"
 #include "host_reader.inc"
+#include "host_subset.inc"
 #include "host_inflate.inc"
 #include "host_inflate_members.inc"
 #include "host_likelihood_file.inc"
