@@ -285,7 +285,8 @@ __global__ __launch_bounds__(256) void k_dense_big_passB(const Scalars *sc, cons
           S0 = S0 * f + 1.0;
           S1 = S1 * f + (x - y);
           m = y;
-        } else {
+        } else if (y > -INFINITY) {  // (u_g = -inf, a weight EM's M-step clamped at 0: the cell adds nothing -- but
+                                     // exp(-inf - m) is NaN while m is still -inf, and so is 0 * (x - y))
           const double p = exp(y - m);
           S0 += p;
           S1 += p * (x - y);
