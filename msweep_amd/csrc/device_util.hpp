@@ -211,6 +211,16 @@ __device__ __forceinline__ double fx_factor(double e, int expbits) {
   return __hiloint2double(hi > ms ? hi : ms, __double2loint(e));
 #endif
 }
+// double -> integer by the magic-number trick: for |q| < 2^51 the low 52 bits of (q + 1.5 * 2^52) hold
+// rint(q) in two's complement; subtracting the magic's bit pattern leaves it as a 64-bit integer.  The
+// magic's low dword is zero: the subtraction is ONE 32-bit operation on the high dword.
+constexpr double kFxMagic = 6755399441055744.0;             // 1.5 * 2^52 = 0x4338000000000000
+constexpr unsigned long long kFxMagicBits = 0x4338000000000000ull;
+__device__ __forceinline__ unsigned long long fx_bits(double scaled_r, double pk) {
+  const double v = fma(scaled_r, pk, kFxMagic);
+  const uint32_t hi = (uint32_t)__double2hiint(v) - (uint32_t)(kFxMagicBits >> 32);
+  return ((unsigned long long)hi << 32) | (uint32_t)__double2loint(v);
+}
 // reference value of a pass's tables: exp(a (T - tref)) <= 1 for every table value T and for log zi
 __device__ __forceinline__ double tref_of(double a, double tmax, double tmin) { return a >= 0.0 ? tmax : tmin; }
 // s for a pass: 9 + ceil(log2(xb / p0)), at least 9

@@ -206,17 +206,11 @@ __device__ __forceinline__ void em_passB_f32_body(unsigned char *smem, const Sca
     }
   };
   const float p0 = (float)uniform_d(sc->p0), zbase = p0 * (float)uniform_d(sc->U);
-  const float gthr = fmaxf(zbase * (float)kGuardRatio, 1.17549435e-38f);
-  const uint32_t gcnt_off = scratch_off + 128u;
-  typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-  auto defer = [&](uint32_t p) {
-    const uint32_t i = __hip_atomic_fetch_add((lds_u32_t *)(size_t)gcnt_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (i < GD.cap) GD.list[(size_t)blockIdx.x * GD.cap + i] = p;
-    else *GD.err = 2;
-  };
+  const GuardQueue<float> gq(GD, scratch_off, zbase);  // ECs whose Z falls below gthr are set aside (guard.hpp)
+  const float gthr = gq.threshold();
   double s_clogZ = 0.0, s_W = 0.0;  // sums over millions of ECs: fp64 accumulators of fp32 terms (file header)
   if (skip) return;
-  if (tid == 0) *(lds_u32_t *)(size_t)gcnt_off = 0u;
+  gq.reset(tid);
   __syncthreads();
 
   // Z, r, the EC's log-likelihood term and W for one EC whose row sum is zs; returns r (0: nothing to scatter)
@@ -224,7 +218,7 @@ __device__ __forceinline__ void em_passB_f32_body(unsigned char *smem, const Sca
     const float Z = zbase + zs;
     if (c == 0.0f) return 0.0f;
     if (!(Z >= gthr)) {
-      if (spoke) defer(pos);
+      if (spoke) gq.defer(pos);
       return 0.0f;
     }
     const float rj = c / Z;
@@ -335,60 +329,15 @@ __device__ __forceinline__ void em_passB_f32_body(unsigned char *smem, const Sca
         add(rc, rj * (E_(rc, fcold) * X_(rc, fcold)), c < narrow_c, fcold);
       }
   }
-  // guarded ECs (sell.hpp): as in k_passB -- a wavefront each, every group visited, fp64 (rare path); each group
-  // receives its share of c_j through the two global fixed-point limbs k_redfin adds to N_g
+  // guarded ECs (guard.hpp): pass B's evaluation in its fp32 form -- fp64 arithmetic (rare path) on float-rounded values
   __syncthreads();
-  const uint32_t n_guard = min(*(lds_u32_t *)(size_t)gcnt_off, GD.cap);
-  if (n_guard) {
+  if (const uint32_t n_guard = gq.count()) {
     if (tid == 0) atomicAdd(GD.visits, (unsigned long long)n_guard);
-    const uint32_t wv = uniform(tid >> 6), nwv = NT / 64;
-    uint32_t *bits = GD.bits + (size_t)(blockIdx.x * 16 + wv) * GD.words;
-    const double logzi = uniform_d(sc->logzi), tref = uniform_d(sc->tref), p0d = uniform_d(sc->p0);
-    const double tls = uniform_d(sc->fx_tscale);
-    auto add_share = [&](uint32_t g, double share) {
-      const double vh = fma(share, tls, kFxMagic);
-      const double qh = vh - kFxMagic;
-      const double ql = fma(share, tls, -qh) * 0x1p36;
-      atomicAdd(&GD.tail[2 * (size_t)g], fx_bits(1.0, qh));
-      atomicAdd(&GD.tail[2 * (size_t)g + 1], fx_bits(1.0, ql));
-    };
-    (void)logzi;
-    for (uint32_t i = wv; i < n_guard; i += nwv) {
-      const uint32_t p = GD.list[(size_t)blockIdx.x * GD.cap + i];
-      const double c = S.cvec[p];
-      double z = 0.0;
-      wave_cells<ENC>(S, p, (uint32_t)lane, [&](uint32_t g, double T) {
-        atomicOr(&bits[g >> 5], 1u << (g & 31));
-        z += e_g[g] * exp((double)(float)T - tref);
-      });
-      __builtin_amdgcn_s_waitcnt(0);
-      double r0 = 0.0;
-      for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) {
-        const uint32_t listed = atomicOr(&bits[w0], 0u);
-        for (uint32_t b = 0; b < 32; ++b) {
-          const uint32_t g = w0 * 32 + b;
-          if (g < G && !((listed >> b) & 1u)) r0 += e_g[g];
-        }
-      }
-      z = wave_sum(z), r0 = wave_sum(r0);
-      const double Z = fma(p0d, r0, z);
-      if (Z > 0.0) {
-        const double rj = c / Z;
-        if (lane == 0) s_clogZ += c * log(Z);
-        wave_cells<ENC>(S, p, (uint32_t)lane, [&](uint32_t g, double T) {
-          add_share(g, e_g[g] * rj * exp((double)(float)T - tref));
-        });
-        for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) {
-          const uint32_t listed = atomicAnd(&bits[w0], 0u);
-          for (uint32_t b = 0; b < 32; ++b) {
-            const uint32_t g = w0 * 32 + b;
-            if (g < G && !((listed >> b) & 1u)) add_share(g, e_g[g] * (rj * p0d));
-          }
-        }
-      } else {
-        if (lane == 0) *GD.err = 1;
-        for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) atomicAnd(&bits[w0], 0u);
-      }
+    const double tref = uniform_d(sc->tref), p0d = uniform_d(sc->p0), tls = uniform_d(sc->fx_tscale);
+    const uint32_t wv = uniform(tid >> 6);
+    for (uint32_t i = wv; i < n_guard; i += NT / 64) {  // (the F32 form reads neither a nor logzi: 1.0, 0.0 stand in)
+      guard_eval_B<ENC, true>(S, GD, gq.bits(wv), gq.entry(i), (uint32_t)lane, G, e_g, 1.0, tref, p0d, 0.0, tls,
+                              [&](double c, double Z, double, double) { s_clogZ += c * log(Z); });
       __builtin_amdgcn_s_waitcnt(0);
     }
   }

@@ -1,6 +1,7 @@
 // gamma_kernels.hpp -- materialisation of gamma / the dense likelihood (utility, not timed).
 #pragma once
 #include "device_util.hpp"
+#include "guard.hpp"
 #include "sell.hpp"
 
 namespace msw {
@@ -37,7 +38,7 @@ __device__ __forceinline__ double gamma_lse(const SellDev &S, uint32_t p, double
   double zs = 0.0;
   for_each_cell<ENC>(S, p, [&](uint32_t g, double T) { zs += exp(u[g] - M) * (exp(a * (T - tref)) - p0); });
   double Z = p0 * U + zs;
-  if (!(Z >= p0 * U * kGuardRatio)) {  // guarded EC (sell.hpp): every group visited instead
+  if (!(Z >= p0 * U * kGuardRatio)) {  // guarded EC (guard.hpp): every group visited instead
     Z = 0.0;
     for (uint32_t g = 0; g < S.n_groups; ++g) {
       double xg = p0;

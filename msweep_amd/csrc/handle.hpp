@@ -21,6 +21,7 @@
 
 #include "common.hpp"
 #include "device_util.hpp"
+#include "guard.hpp"
 #include "sell.hpp"
 #include "comm.hpp"
 #include "text_cells.hpp"
@@ -80,7 +81,7 @@ struct Resident : LikShape {
   int n_tab_inline() const { return flavor == 0 && n_area <= (uint32_t)kTabInline ? (int)n_area : 0; }
   // rows of per-workgroup (or per-wave) column-sum partials pass B leaves for k_redfin
   int npart_rows() const { return flavor == 0 ? nblk : (nreg >= 32 ? 4 * nblk_dense : nblk_dense); }
-  // guarded ECs (sell.hpp), CSR flavour: room in a workgroup's list for every EC it can see (its wavefronts take
+  // guarded ECs (guard.hpp), CSR flavour: room in a workgroup's list for every EC it can see (its wavefronts take
   // slices -- and long ECs -- round-robin, SliceStream's stride), and words of a wavefront's bitmap of groups
   uint32_t guard_cap() const {
     static_assert(kPassThreads / 64 <= 16 && kPassThreadsB / 64 <= 16, "guard_cap / guard_bits assume <= 16 wavefronts per workgroup");
@@ -112,7 +113,7 @@ struct Solver {
   DevBuf<double> partA, partS, partAcc, partC, partR, totS;
   size_t lds_attr[3][80] = {};  // dynamic-LDS limit already granted per sweep instantiation ([2]: pass B's short-slice ones)
   DevBuf<double> commA, commB;  // 1 and G + 4 doubles
-  // guarded ECs (sell.hpp): per-workgroup lists, per-wavefront bitmaps, error flag
+  // guarded ECs (guard.hpp): per-workgroup lists, per-wavefront bitmaps, error flag
   DevBuf<uint32_t> guard_list, guard_bits;
   DevBuf<unsigned long long> guard_tail;  // [2 G] the guarded ECs' shares per group, two fixed-point limbs
   DevBuf<int> guard_err;

@@ -294,7 +294,7 @@ __device__ __forceinline__ void for_each_cell(const SellDev &S, uint32_t p, F f)
 }
 
 // The cells of the EC at permuted position p, one per lane and step, for a whole wavefront:
-// f(group id, log-likelihood).  Sentinel padding is skipped.  (Rare-path code: the guarded ECs.)
+// f(group id, log-likelihood).  Sentinel padding is skipped.  (Rare-path code: the guarded ECs, guard.hpp.)
 template <int ENC, class F>
 __device__ __forceinline__ void wave_cells(const SellDev &S, uint32_t p, uint32_t lane, F f) {
   using R = Rec<ENC>;
@@ -317,29 +317,6 @@ __device__ __forceinline__ void wave_cells(const SellDev &S, uint32_t p, uint32_
     }
   }
 }
-
-// ---------------------------------------------------------------------------------------
-// Guarded ECs (SURVEY.md 7.3 ii).  The sweeps form Z_j = p0 * U + sum_listed e_g (x_gj - p0): when
-// the listed groups hold nearly all of U and their cells sit far below the background (x << p0:
-// an isolate's read that hits the dominant lineage with one k-mer, priors << 1) the two parts cancel
-// and Z_j, r_j = c_j / Z_j and the listed groups' column sums lose their digits -- or their sign.
-// An EC whose Z_j comes out below 2^-8 of the background sum (the unguarded relative error is thus
-// at most 2^-45; with the reference's WOR21 tables, whose values stay within e^-1 of log(zi) up to
-// groups of 400 sequences, no EC comes near it) is set aside by the sweep (its position appended to the workgroup's list) and
-// evaluated WITHOUT the background trick at the end of the workgroup, a wavefront per EC:
-// Z_j = sum_listed e_g x_gj + p0 * (sum over the groups NOT listed, one by one), and every group's
-// share of c_j added directly.  O(G) per guarded EC; none exist in ordinary inputs.
-// ---------------------------------------------------------------------------------------
-constexpr double kGuardRatio = 0x1p-8;
-struct GuardDev {
-  uint32_t *list;          // [workgroups * cap] positions of the ECs set aside, per workgroup
-  uint32_t *bits;          // [workgroups * 16 * words] one bitmap of listed groups per wavefront
-  unsigned long long *tail;  // [2 * G] the guarded ECs' shares per group, two fixed-point limbs (pass B)
-  const double *lut_area;  // table value of every slot-area entry
-  int *err;                // set when an EC has no probability under any group
-  unsigned long long *visits;  // ECs pass B has taken through the guard path so far (reporting: msw_core_guarded_visits)
-  uint32_t cap, words;
-};
 
 // LDS image of the sweeps (byte offsets; bhi = sell_bhi(n_tab_lds)):
 //   [0, 16 * n_tab_lds)                 slot area: 16-byte per-slot entries of the pass -- all of them (tlds), the

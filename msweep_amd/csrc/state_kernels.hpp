@@ -6,6 +6,7 @@
 // One "slot" = k_passA -> k_finstep -> k_passB -> k_redfin (k_finstep below says what a slot does).
 #pragma once
 #include "device_util.hpp"
+#include "guard.hpp"
 
 namespace msw {
 
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(kRedfinThreads) void k_redfin(const Scalars *sc, in
   const bool mathlane = (tid & 63) < kRedfinGroups && tid < 128 && g < G;
   const int role = tid >> 6;
   double ug0 = 0.0, eg0 = 0.0, al0 = 0.0;
-  long long th = 0, tl = 0;  // the guarded ECs' shares of the group (sell.hpp), two fixed-point limbs
+  long long th = 0, tl = 0;  // the guarded ECs' shares of the group, two fixed-point limbs (guard.hpp guard_share_join)
   if (mathlane) {
     ug0 = u[g];
     eg0 = e[g];
@@ -485,11 +486,11 @@ __global__ __launch_bounds__(kRedfinThreads) void k_redfin(const Scalars *sc, in
           ((unsigned long long)(uint32_t)__double2loint(th1 + 6755399441055744.0) << 32) + (unsigned long long)__double2ll_rn(tl1);
       const long long tot = (long long)((unsigned long long)ai + b);
       nc = fmax((double)tot * s0.fx_inv * (eg0 / fg), 0.0);
-      nc += (double)th * s0.fx_tinv + (double)tl * (s0.fx_tinv * 0x1p-36);
+      nc += guard_share_join(th, tl, s0.fx_tinv);
       muv = (s0.M - ug) * nc;
     } else if (flavor == 0) {
       nc = eg0 * (s0.p0 * W + A);
-      nc += (double)th * s0.fx_tinv + (double)tl * (s0.fx_tinv * 0x1p-36);
+      nc += guard_share_join(th, tl, s0.fx_tinv);
       muv = (s0.M - ug) * nc;
     } else {
       nc = A;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "device_util.hpp"
+#include "guard.hpp"
 #include "sell.hpp"
 
 namespace msw {
@@ -58,20 +59,11 @@ constexpr bool kPrimeFirstSlice = true;
 // runs of a solve are bit-identical (fp64 atomics: the stop test sits in their rounding noise and a
 // 10 M-read run stopped at 209 or 210 iterations), and the totals are the same whatever the number of
 // workgroups or ranks the ECs are spread over.  2^K = Scalars::fx_scale, sum c * 2^K < 2^61.
-// MSW_FX=0 builds the fp64-atomic sweeps (A/B timing only); kFx lives in common.hpp.
-// double -> integer by the magic-number trick: for |q| < 2^51 the low 52 bits of (q + 1.5 * 2^52) hold
-// rint(q) in two's complement; subtracting the magic's bit pattern leaves it as a 64-bit integer.  The
-// magic's low dword is zero: the subtraction is ONE 32-bit operation on the high dword.
-constexpr double kFxMagic = 6755399441055744.0;             // 1.5 * 2^52 = 0x4338000000000000
-constexpr unsigned long long kFxMagicBits = 0x4338000000000000ull;
-__device__ __forceinline__ unsigned long long fx_bits(double scaled_r, double pk) {
-  const double v = fma(scaled_r, pk, kFxMagic);
-  const uint32_t hi = (uint32_t)__double2hiint(v) - (uint32_t)(kFxMagicBits >> 32);
-  return ((unsigned long long)hi << 32) | (uint32_t)__double2loint(v);
-}
+// MSW_FX=0 builds the fp64-atomic sweeps (A/B timing only); kFx lives in common.hpp; the conversion itself
+// (fx_bits) in device_util.hpp.
 
 // c / z and 1 / z for the EC epilogues of the sweeps: z is a softmax denominator that passed the guard test
-// (sell.hpp) -- a normal number between 2^-8 of the background sum and twice the number of groups -- so the
+// (guard.hpp) -- a normal number between 2^-8 of the background sum and twice the number of groups -- so the
 // operand scaling and the special-case fix-up of the IEEE division (4 of its 12 instructions, 7 of 12 for a
 // reciprocal) are not needed.  Reciprocal estimate and two Newton steps (within an ulp of 1 / z), times c: within
 // two ulps of the quotient -- the residual correction that brought it to one (two more operations per EC: round 4
@@ -440,21 +432,15 @@ __global__ __launch_bounds__(pass_threads_A<ENC>()) void k_passA(const Scalars *
   };
   const double p0 = uniform_d(sc->p0), U = uniform_d(sc->U);
   const double zbase = p0 * U;
-  const double gthr = fmax(zbase * kGuardRatio, 2.2250738585072014e-308);  // (Z = 0 is set aside too: reported, not divided by)  // ECs whose Z falls below it are set aside (sell.hpp, guarded ECs)
-  const uint32_t gcnt_off = scratch_off + 128u;
-  typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-  auto defer = [&](uint32_t p) {
-    const uint32_t i = __hip_atomic_fetch_add((lds_u32_t *)(size_t)gcnt_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (i < GD.cap) GD.list[(size_t)blockIdx.x * GD.cap + i] = p;
-    else *GD.err = 2;  // cannot happen while guard_cap mirrors the stride distribution (alloc_solve_state)
-  };
+  const GuardQueue<double> gq(GD, scratch_off, zbase);  // ECs whose Z falls below gthr are set aside (guard.hpp)
+  const double gthr = gq.threshold();
   double nn = 0.0;
   if (skip) return;
-  if (tid == 0) *(lds_u32_t *)(size_t)gcnt_off = 0u;
+  gq.reset(tid);
   if (tid < 64) {  // (wave-uniform)
     m1 = wave_sum(m1);
     m2 = wave_sum(m2);
-    if (tid == 0) sh[18] = m1, sh[19] = m2;  // (reduction scratch: doubles 0..15 the block sums, byte 128 the guard counter)
+    if (tid == 0) sh[18] = m1, sh[19] = m2;  // (reduction scratch: doubles 0..15 the block sums, 16 the guard count -- guard.hpp)
   }
   if (tid == 0 && blockIdx.x == 0) MSW_STAMP(sc->iter, 0, 0);
   __syncthreads();
@@ -575,7 +561,7 @@ __global__ __launch_bounds__(pass_threads_A<ENC>()) void k_passA(const Scalars *
         const double S1 = (b1 + c.t1) * iZ, S2 = (b2 + c.t2) * iZ;
         nn += S2 - S1 * S1;
       } else {
-        defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 + ((uint32_t)lane >> lgm) : sb.sl * 64 + lane));
+        gq.defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 + ((uint32_t)lane >> lgm) : sb.sl * 64 + lane));
       }
     }
   };
@@ -633,7 +619,7 @@ __global__ __launch_bounds__(pass_threads_A<ENC>()) void k_passA(const Scalars *
             const double S1 = (b1 + t1) * iZ, S2 = (b2 + t2) * iZ;
             nn += S2 - S1 * S1;
           } else {
-            defer(r);
+            gq.defer(r);
           }
         }
         c = {0.0, 0.0, 0.0};
@@ -643,39 +629,21 @@ __global__ __launch_bounds__(pass_threads_A<ENC>()) void k_passA(const Scalars *
       r = nr, kb = nkb, k1 = nk1, have = nhave;
     }
   }
-  // guarded ECs (sell.hpp): a wavefront each, every group visited -- no background term to cancel against
+  // guarded ECs (guard.hpp): a wavefront each, every group visited -- no background term to cancel against
   __syncthreads();
-  const uint32_t n_guard = min(*(lds_u32_t *)(size_t)gcnt_off, GD.cap);
-  if (n_guard) {
-    const uint32_t wv = uniform(tid >> 6), nwv = NT / 64;
-    uint32_t *bits = GD.bits + (size_t)(blockIdx.x * 16 + wv) * GD.words;
+  if (const uint32_t n_guard = gq.count()) {
     const double a = uniform_d(sc->a), oma = 1.0 - a, logzi = uniform_d(sc->logzi), tref = uniform_d(sc->tref);
-    for (uint32_t i = wv; i < n_guard; i += nwv) {
-      const uint32_t p = GD.list[(size_t)blockIdx.x * GD.cap + i];
+    const uint32_t wv = uniform(tid >> 6);
+    for (uint32_t i = wv; i < n_guard; i += NT / 64) {
       double z = 0.0, t1 = 0.0, t2 = 0.0;
-      wave_cells<ENC>(S, p, (uint32_t)lane, [&](uint32_t g, double T) {
-        const double x = exp(a * (T - tref)), sv = oma * (T - logzi) + ew_g[g].y;
-        const double q = ew_g[g].x * x;
-        atomicOr(&bits[g >> 5], 1u << (g & 31));
-        z += q;
-        t1 = fma(q, sv, t1);
-        t2 = fma(q * sv, sv, t2);
+      guard_walk<ENC, true, true>(S, GD, gq.bits(wv), gq.entry(i), (uint32_t)lane, G, [&](uint32_t g, double T) {
+        const double x = exp(a * (T - tref)), sv = oma * (T - logzi) + ew_g[g].y, q = ew_g[g].x * x;
+        z += q, t1 = fma(q, sv, t1), t2 = fma(q * sv, sv, t2);
+      }, [&](uint32_t g) {
+        const double2 ev = ew_g[g];
+        const double q = ev.x * p0;
+        z += q, t1 = fma(q, ev.y, t1), t2 = fma(q * ev.y, ev.y, t2);
       });
-      __builtin_amdgcn_s_waitcnt(0);  // the bitmap updates have reached memory before it is read back
-      for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) {
-        const uint32_t listed = atomicOr(&bits[w0], 0u);
-        for (uint32_t b = 0; b < 32; ++b) {
-          const uint32_t g = w0 * 32 + b;
-          if (g < G && !((listed >> b) & 1u)) {
-            const double2 ev = ew_g[g];
-            const double q = ev.x * p0;
-            z += q;
-            t1 = fma(q, ev.y, t1);
-            t2 = fma(q * ev.y, ev.y, t2);
-          }
-        }
-        atomicAnd(&bits[w0], 0u);
-      }
       z = wave_sum(z), t1 = wave_sum(t1), t2 = wave_sum(t2);
       if (lane == 0) {
         if (z > 0.0) {
@@ -839,14 +807,8 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
   const int fxe = (int)uniform((uint32_t)fx_expbits(sc->fx_shift));
   const double fxs = uniform_d(sc->fx_scale), fxb = ldexp(uniform_d(sc->xb), 1 - (int)uniform((uint32_t)sc->fx_shift));
   const double fxt1 = 0x1p51 / fxs, fxt2 = 0x1p51 / (fxs * fxb);  // the narrow-add test of an EC (below)
-  const double gthr = fmax(zbase * kGuardRatio, 2.2250738585072014e-308);  // (Z = 0 is set aside too: reported, not divided by)  // ECs whose Z falls below it are set aside (sell.hpp, guarded ECs)
-  const uint32_t gcnt_off = scratch_off + 128u;
-  typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-  auto defer = [&](uint32_t p) {
-    const uint32_t i = __hip_atomic_fetch_add((lds_u32_t *)(size_t)gcnt_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (i < GD.cap) GD.list[(size_t)blockIdx.x * GD.cap + i] = p;
-    else *GD.err = 2;  // cannot happen while guard_cap mirrors the stride distribution (alloc_solve_state)
-  };
+  const GuardQueue<double> gq(GD, scratch_off, zbase);  // ECs whose Z falls below gthr are set aside (guard.hpp)
+  const double gthr = gq.threshold();
   double s_clogZ = 0.0, s_rH = 0.0, s_W = 0.0;
   double lp_mant = 1.0;  // deferred logarithms: product of mantissas in [2^-960, 1] ...
   int lp_exp = 0;        // ... and sum of exponents, per lane
@@ -856,7 +818,7 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
     lp_exp = 0;
   };
   if (skip) return;
-  if (tid == 0) *(lds_u32_t *)(size_t)gcnt_off = 0u;
+  gq.reset(tid);
   if (tid == 0 && blockIdx.x == 0) MSW_STAMP(sc->iter, 2, 0);
   __syncthreads();
   if (tid == 0 && blockIdx.x == 0) MSW_STAMP(sc->iter, 2, 1);
@@ -1041,7 +1003,7 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
         spoke = ((uint32_t)lane & ((1u << lgm) - 1u)) == 0u;
       }
       if (c != 0.0 && !(zbase + zs >= gthr)) {
-        if (spoke) defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 + ((uint32_t)lane >> lgm) : sb.sl * 64 + lane));
+        if (spoke) gq.defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 + ((uint32_t)lane >> lgm) : sb.sl * 64 + lane));
       } else if (c != 0.0) {
         const double Z = zbase + zs;
         const double rj = ec_div(c, Z);
@@ -1111,7 +1073,7 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
         pairs_any(t, n);
       }
       if (c != 0.0 && !(zbase + zs >= gthr)) {  // (slices of more than 16 rows hold one lane per EC: lgm = 0)
-        defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 : sb.sl * 64) + lane);
+        gq.defer(S.n_long + (ML ? slice_geo(S.cls, sb.sl).ec0 : sb.sl * 64) + lane);
       } else if (c != 0.0) {
         const double Z = zbase + zs;
         const double rj = ec_div(c, Z);
@@ -1191,7 +1153,7 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
       zs = wave_sum(zs);
       hs = wave_sum(hs);
       if (c != 0.0 && !(zbase + zs >= gthr)) {  // wave-uniform
-        if (lane == 0) defer(r);
+        if (lane == 0) gq.defer(r);
       } else if (c != 0.0) {
         const double Z = zbase + zs;
         const double rj = ec_div(c, Z);
@@ -1258,69 +1220,15 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
     }
     flush_logs();
   }
-  // guarded ECs (sell.hpp): a wavefront each, every group visited.  Each group receives its share of the
-  // EC's c_j directly -- listed: c e_g x / Z, not listed: c e_g p0 / Z -- and the EC stays out of
-  // W = sum r_j (the background share of the ordinary ECs).
+  // guarded ECs (guard.hpp): a wavefront each, every group visited, its share of the EC's c_j added directly
   __syncthreads();
-  const uint32_t n_guard = (GMODE != 4 || rg.first) ? min(*(lds_u32_t *)(size_t)gcnt_off, GD.cap) : 0u;  // once, not per range run
-  if (n_guard) {
+  if (const uint32_t n_guard = (GMODE != 4 || rg.first) ? gq.count() : 0u) {  // once, not per range run
     if (tid == 0) atomicAdd(GD.visits, (unsigned long long)n_guard);
-    const uint32_t wv = uniform(tid >> 6), nwv = NT / 64;
-    uint32_t *bits = GD.bits + (size_t)(blockIdx.x * 16 + wv) * GD.words;
-    const double a = uniform_d(sc->a), logzi = uniform_d(sc->logzi), tref = uniform_d(sc->tref);
-    // A group's share of a guarded EC, in reads, goes to two global 64-bit fixed-point accumulators
-    // of the group (units 2^-t and 2^-(t+36) reads, 2^t = Scalars::fx_tscale): such a share can exceed any
-    // bound the group's own exponent allows for (c e_g p0 / Z with Z far below the background sum),
-    // while the shares of one EC always add up to c_j.  Global integer atomics: rare path.
-    const double tls = uniform_d(sc->fx_tscale);
-    auto add_share = [&](uint32_t g, double share) {
-      const double vh = fma(share, tls, kFxMagic);
-      const double qh = vh - kFxMagic;                     // rint(share * 2^t), exact
-      const double ql = fma(share, tls, -qh) * 0x1p36;     // remainder, |.| <= 2^35
-      atomicAdd(&GD.tail[2 * (size_t)g], fx_bits(1.0, qh));
-      atomicAdd(&GD.tail[2 * (size_t)g + 1], fx_bits(1.0, ql));
-    };
-    for (uint32_t i = wv; i < n_guard; i += nwv) {
-      const uint32_t p = GD.list[(size_t)blockIdx.x * GD.cap + i];
-      const double c = S.cvec[p];
-      double z = 0.0, h = 0.0;
-      wave_cells<ENC>(S, p, (uint32_t)lane, [&](uint32_t g, double T) {
-        const double q = e_g[g] * exp(a * (T - tref));
-        atomicOr(&bits[g >> 5], 1u << (g & 31));
-        z += q;
-        h = fma(q, T, h);
-      });
-      __builtin_amdgcn_s_waitcnt(0);  // the bitmap updates have reached memory before it is read back
-      double r0 = 0.0;
-      for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) {
-        const uint32_t listed = atomicOr(&bits[w0], 0u);
-        for (uint32_t b = 0; b < 32; ++b) {
-          const uint32_t g = w0 * 32 + b;
-          if (g < G && !((listed >> b) & 1u)) r0 += e_g[g];
-        }
-      }
-      z = wave_sum(z), h = wave_sum(h), r0 = wave_sum(r0);
-      const double Z = fma(p0, r0, z), H = fma(p0 * logzi, r0, h);
-      if (Z > 0.0) {
-        const double rj = c / Z;
-        if (lane == 0) {
-          s_clogZ += c * log(Z);
-          s_rH += rj * H;
-        }
-        wave_cells<ENC>(S, p, (uint32_t)lane, [&](uint32_t g, double T) {
-          add_share(g, e_g[g] * rj * exp(a * (T - tref)));
-        });
-        for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) {
-          const uint32_t listed = atomicAnd(&bits[w0], 0u);  // read and clear
-          for (uint32_t b = 0; b < 32; ++b) {
-            const uint32_t g = w0 * 32 + b;
-            if (g < G && !((listed >> b) & 1u)) add_share(g, e_g[g] * (rj * p0));
-          }
-        }
-      } else {
-        if (lane == 0) *GD.err = 1;  // no probability under any group: the solve reports it
-        for (uint32_t w0 = lane; w0 < GD.words; w0 += 64) atomicAnd(&bits[w0], 0u);
-      }
+    const double a = uniform_d(sc->a), logzi = uniform_d(sc->logzi), tref = uniform_d(sc->tref), tls = uniform_d(sc->fx_tscale);
+    const uint32_t wv = uniform(tid >> 6);
+    for (uint32_t i = wv; i < n_guard; i += NT / 64) {
+      guard_eval_B<ENC, false>(S, GD, gq.bits(wv), gq.entry(i), (uint32_t)lane, G, e_g, a, tref, p0, logzi, tls,
+                               [&](double c, double Z, double rj, double H) { s_clogZ += c * log(Z), s_rH += rj * H; });
       __builtin_amdgcn_s_waitcnt(0);
     }
   }
