@@ -133,6 +133,8 @@ typedef struct msw_layout_info {
   int32_t passB_reg_cells;     /* records per slice lane pass B holds in registers: 16, or 8 = its short-slice instantiation
                                 * with 16 wavefronts per workgroup (slices of > 8 rows hold <= 1/20 of the rows) */
   uint64_t rows_over_8;        /* rows of the slices of more than 8 rows (0 when not counted: index / wide / value records) */
+  int32_t passB_waves;         /* wavefronts per workgroup of the k_passB instantiation this layout is swept with */
+  int32_t pad_;
 } msw_layout_info;
 int msw_core_layout_info(msw_handle h, msw_layout_info *out);
 /* Whether the NEXT likelihood made resident on the handle (msw_core_set_csr, msw_core_build_likelihood, a dense

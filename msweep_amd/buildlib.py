@@ -19,6 +19,12 @@ ABI_UNIT = "msweep_core"    # the only unit that sees MSW_SRC_HASH
 # longest first: the pool starts them in this order
 UNITS = ["sweep_index", "sweep_narrow", "sweep_wide", "input", "build", "prim", "output", "sweep_dense", "solve", ABI_UNIT]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# Pass B's 16-row kernel over offset records at 16 wavefronts per workgroup (common.hpp MSW_PASS_THREADS_B16: kernels, launches
+# and layout_info follow the one constant, so every unit sees it) goes with its unit compiled without machine-level
+# loop-invariant hoisting: hoisted constants cost the kernel 20 registers (143 -> 123) and, under the 128 of 16 wavefronts, scratch
+# (tests/test_passB_wave16_resources.py holds the built code objects to 128 registers and no scratch).
+WAVE16_FLAGS = ["-DMSW_PASS_THREADS_B16=1024"]
+UNIT_FLAGS = {"sweep_narrow": ["-mllvm", "-disable-machine-licm"]}
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-lz", "-Wl,-rpath,/opt/rocm/lib"]
 MAX_JOBS = 16
 
@@ -116,7 +122,8 @@ def record(obj, flags, cwd=CSRC):
 
 
 def unit_flags(unit, extra_flags, src_hash):
-    return FLAGS + list(extra_flags) + ([f'-DMSW_SRC_HASH="{src_hash}"'] if unit == ABI_UNIT else [])
+    return (FLAGS + WAVE16_FLAGS + UNIT_FLAGS.get(unit, []) + list(extra_flags)
+            + ([f'-DMSW_SRC_HASH="{src_hash}"'] if unit == ABI_UNIT else []))
 
 
 def build_library(out=LIB, extra_flags=(), jobs=None, build_dir=None, log=None):

@@ -115,7 +115,7 @@ class LayoutInfo(C.Structure):
                 ("slot_entries_in_lds", C.c_uint32), ("n_slices", C.c_uint32), ("n_long_ecs", C.c_uint32),
                 ("rows", C.c_uint64), ("rows_from_memory", C.c_uint64), ("slices_by_lanes", C.c_uint32 * 7),
                 ("max_rows", C.c_uint32), ("bank_scheduled", C.c_int32), ("passB_reg_cells", C.c_int32),
-                ("rows_over_8", C.c_uint64)]
+                ("rows_over_8", C.c_uint64), ("passB_waves", C.c_int32), ("pad_", C.c_int32)]
 
 
 class BootstrapTiming(C.Structure):
@@ -604,7 +604,8 @@ class Core:
         """How the resident CSR-of-ECs likelihood is laid out for the sweeps (msw_core_layout_info)."""
         t = LayoutInfo()
         self._check(self._L.msw_core_layout_info(self._h, C.byref(t)))
-        return {k: (list(getattr(t, k)) if k == "slices_by_lanes" else getattr(t, k)) for k, _ in LayoutInfo._fields_}
+        return {k: (list(getattr(t, k)) if k == "slices_by_lanes" else getattr(t, k)) for k, _ in LayoutInfo._fields_
+                if k != "pad_"}
 
     def layout_hash(self):
         out = C.c_uint64(0)

@@ -82,6 +82,11 @@ int msw_core_layout_info(msw_handle h, msw_layout_info *out) {
     li.bank_scheduled = L.packed_scheduled ? 1 : 0;
     li.passB_reg_cells = L.passB_rc8 ? 8 : kRegCells;
     li.rows_over_8 = L.rows_over8;
+    {  // (the instantiation launch_passB_t picks: sweep_launch.hpp)
+      const bool ml = L.cls.s0[kSliceClasses - 1] > 0;
+      const int rc = L.enc == kEncNarrow && L.passB_rc8 && !ml ? 8 : kRegCells;
+      li.passB_waves = pass_threads_B_of(L.enc, L.gmodeB, L.tlds, rc) / kWave;
+    }
     std::vector<uint32_t> off((size_t)L.nslices + 1);
     MSW_HIP(hipMemcpy(off.data(), L.slice_off.p, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     li.rows = off[L.nslices];

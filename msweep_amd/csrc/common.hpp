@@ -11,9 +11,10 @@
 namespace msw {
 
 constexpr int kWave = 64;          // CDNA wavefront
-// One persistent workgroup per CU for the CSR sweeps.  Pass A: 16 wavefronts.  Pass B: 12, i.e. 168
-// instead of 128 registers per lane -- enough to keep an EC's 16 x - p0 between the row sum and the
-// scatter (no second gather); measured 3 % faster than 16 wavefronts with the hybrid.
+// One persistent workgroup per CU for the CSR sweeps.  Pass A: 16 wavefronts.  Pass B: 16 where the kernel keeps an
+// EC's 16 x - p0 between the row sum and the scatter within 128 registers per lane (the short-slice kernel, and the
+// 16-row kernel over offset records with everything in LDS: below), else 12, i.e. 168 registers -- a second gather or a
+// scratch reload costs more than the fourth wavefront per SIMD brings (index records: 12 measured 3 % faster than 16).
 #ifndef MSW_PASS_THREADS_A
 #define MSW_PASS_THREADS_A 1024
 #endif
@@ -27,6 +28,15 @@ constexpr int kWave = 64;          // CDNA wavefront
 constexpr int kPassThreads = MSW_PASS_THREADS_A;
 constexpr int kPassThreadsB = MSW_PASS_THREADS_B;
 constexpr int kPassThreadsB8 = MSW_PASS_THREADS_B8;
+// (the 16-row kernel over offset records with everything in LDS, sweep_kernels.hpp pass_threads_B_of: the library is
+// built with -DMSW_PASS_THREADS_B16=1024 -- 16 wavefronts -- TOGETHER with -mllvm -disable-machine-licm for its unit
+// (msweep_amd/buildlib.py): the kernel needs 123 registers, but the compiler's machine-level hoisting parks 20 more of
+// loop-invariant constants across the slice loop, the six coefficients of log() for the rare counts above 15 among them,
+// and under a 128-register bound spills around them.  Compiled without that flag the instantiation keeps 12.)
+#ifndef MSW_PASS_THREADS_B16
+#define MSW_PASS_THREADS_B16 768
+#endif
+constexpr int kPassThreadsB16 = MSW_PASS_THREADS_B16;
 constexpr int kMaxTrace = 4096;
 constexpr int kRedfinParts = 5;    // doubles per workgroup of k_redfin's partial sums (state_kernels.hpp)
 constexpr int kRedfinGroups = 16;  // groups per workgroup of k_redfin

@@ -1,7 +1,7 @@
 // sweep_kernels.hpp -- the two HBM-streaming sweeps of one RCG iteration over the SELL-64
 // likelihood: pass A (natural-gradient norm) and pass B (softmax / column sums / ELBO).
 //
-// Both kernels: one persistent workgroup per CU (pass A 16 wavefronts, pass B 12; value records 8); its
+// Both kernels: one persistent workgroup per CU (pass A 16 wavefronts, pass B 12 or 16 -- pass_threads_B_of; value records 8); its
 // wavefronts take slices round-robin.  A slice of up to kRegCells cells per EC is held in registers: while
 // slice s is being processed the records of the wave's next slice are already in flight (the record stream
 // is the only HBM traffic; everything else is gathered from LDS).  Slice bounds are wave-uniform
@@ -177,8 +177,20 @@ template <int ENC>
 constexpr int pass_threads_A() {
   return ENC == kEncValue ? MSW_VAL_THREADS : (ENC == kEncIndex ? MSW_HYB_THREADS_A : kPassThreads);
 }
-template <int ENC, int RC = kRegCells>
-constexpr int pass_threads_B() { return ENC == kEncValue ? MSW_VAL_THREADS : (RC < kRegCells ? kPassThreadsB8 : kPassThreadsB); }
+// Pass B: what decides the register count decides the wavefronts -- encoding, GMODE, table placement and RC.  The
+// 16-row kernel over offset records with e_g, the column sums and the slot table in LDS (GMODE 1 | 2, TLDS) takes
+// kPassThreadsB16: 16 wavefronts in the library as built (123 registers, no scratch, once its unit is compiled without
+// machine-level hoisting: common.hpp; tests/test_passB_wave16_resources.py holds every instantiation built for 1024
+// threads to 128 registers and no scratch), like the short-slice one; every other instantiation keeps 12.  One function
+// for the kernels' launch bounds, the host's launch dimensions and layout_info.
+constexpr int pass_threads_B_of(int enc, int gmode, bool tlds, int rc) {
+  if (enc == kEncValue) return MSW_VAL_THREADS;
+  if (enc == kEncNarrow && rc < kRegCells) return kPassThreadsB8;
+  if (enc == kEncNarrow && (gmode == 1 || gmode == 2) && tlds) return kPassThreadsB16;
+  return kPassThreadsB;
+}
+template <int ENC, int GMODE, bool TLDS, int RC = kRegCells>
+constexpr int pass_threads_B() { return pass_threads_B_of(ENC, GMODE, TLDS, RC); }
 
 // s_waitcnt vmcnt(0), leaving the other counters alone (gfx9 layout: vmcnt = imm[3:0] | imm[15:14] << 4)
 __device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
@@ -682,7 +694,7 @@ __global__ __launch_bounds__(pass_threads_A<ENC>()) void k_passA(const Scalars *
 // overlapped by the wavefronts of a SIMD: a fourth one is worth 16 % of the sweep at cfg5 (243 -> 204 us in one job).
 // Longer slices take the streaming branch in chunks of 8 rows (host: launch_passB_t picks RC by the rows they hold).
 template <int ENC, int GMODE, bool TLDS, bool ML, int RC = kRegCells>
-__global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Scalars *sc, SellDev S, const double *e_g,
+__global__ __launch_bounds__((pass_threads_B<ENC, GMODE, TLDS, RC>())) void k_passB(const Scalars *sc, SellDev S, const double *e_g,
                                                        const double2 *tabB_g, double *partAcc,
                                                        double *partS, double *accGlobal, RangeB rg, GuardDev GD) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -690,7 +702,7 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
   using RT = typename R::T;
   constexpr bool HYB = ENC == kEncIndex;  // index records + hybrid slot area (see k_passA)
   constexpr bool VAL = ENC == kEncValue;  // value records: no table, exp per cell
-  constexpr int NT = pass_threads_B<ENC, RC>();
+  constexpr int NT = pass_threads_B<ENC, GMODE, TLDS, RC>();
   static_assert(!((HYB || VAL) && TLDS), "index records go with the hybrid slot area, value records have no table");
   constexpr bool TL = TLDS || HYB;
   const RecDec D = rec_dec(S);
@@ -837,9 +849,8 @@ __global__ __launch_bounds__((pass_threads_B<ENC, RC>())) void k_passB(const Sca
     }
     double zs = 0.0, hs = 0.0;
     // row sums: straight-line code per cell count (wave-uniform).  x - p0 of the first KEEPN
-    // cells stays in registers for the scatter, any others are gathered a second time (with 16
-    // wavefronts per workgroup all 16 would push the kernel into scratch, and a scratch reload
-    // drains the record prefetch: hence 12 wavefronts, common.hpp).
+    // cells stays in registers for the scatter, any others are gathered a second time (a scratch reload in the slice
+    // loop drains the record prefetch: the instantiations that do not fit 128 registers run 12 wavefronts, common.hpp).
     constexpr int KEEPN = ENC == kEncWide ? 4 : (MSW_B_KEEPN < RC ? MSW_B_KEEPN : RC);  // 8-byte records take twice the registers
     // (value records keep all 16: the alternative is a second exp per cell)
     double xv[KEEPN > 0 ? KEEPN : 1];

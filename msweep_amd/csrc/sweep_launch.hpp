@@ -44,7 +44,7 @@ void launch_passB_t(const Resident &L, Solver &s) {
         return GM == 4 ? RangeB{g0, std::min<uint32_t>(kRangeGroups, L.G - g0), g0 == 0 ? 1 : 0} : RangeB{0, 0, 1};
       };
       for (uint32_t g0 = 0; g0 < (GM == 4 ? L.G : 1u); g0 += kRangeGroups)
-        hipLaunchKernelGGL(k8, dim3(L.nblk), dim3(pass_threads_B<ENC, 8>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+        hipLaunchKernelGGL(k8, dim3(L.nblk), dim3(pass_threads_B<ENC, GM, TL, 8>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
                            s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p, rg_of(g0), guard_view(L, s));
       return;
     }
@@ -53,12 +53,12 @@ void launch_passB_t(const Resident &L, Solver &s) {
   prepare_sweep(k, lds, s.lds_attr[1][(ml ? 40 : 0) + ENC * 10 + 2 * GM + (TL ? 1 : 0)]);
   if (GM == 4) {  // one run per range of groups; the first also delivers the ELBO terms
     for (uint32_t g0 = 0; g0 < L.G; g0 += kRangeGroups)
-      hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+      hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC, GM, TL>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
                          s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p,
                          RangeB{g0, std::min<uint32_t>(kRangeGroups, L.G - g0), g0 == 0 ? 1 : 0}, guard_view(L, s));
     return;
   }
-  hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
+  hipLaunchKernelGGL(k, dim3(L.nblk), dim3(pass_threads_B<ENC, GM, TL>()), lds, s.stream, s.sc.p, sell_view(L, s), s.e.p,
                      s.tabB.p, s.partAcc.p, s.partS.p, s.Acc.p, RangeB{0, 0, 1}, guard_view(L, s));
 }
 
