@@ -269,6 +269,43 @@ int msw_core_assign_table_block(msw_handle h, size_t row_begin, size_t row_end, 
 int msw_core_assign_table_block_gzip(msw_handle h, size_t row_begin, size_t row_end, const char **out, size_t *len_out,
                                      size_t *text_len_out);
 
+/* --write-read-probs: the read-to-group probabilities of the last solve as SPARSE text formatted on the device
+ * (sparse_probs_kernels.hpp): one line  dec(id) '\t' dec(g) '\t' g6(p) '\n'  per KEPT cell.  Cell (g, j) is kept iff
+ * gamma(g, j) >= log(threshold) -- gamma the very bits msw_core_gamma_block returns, log(threshold) formed once on the
+ * host (*log_thr_out), a NaN compares false --, g over the estimated groups (the rows of the resident likelihood), and
+ * g6(p) is the token MSW_TEXT_PROBS prints for that cell, byte for byte (undecided cells completed on the host as there).
+ * Since the probabilities of an EC sum to 1, an EC keeps at most 1 / threshold cells; they are found from its listed cells
+ * and a prefix of the groups ordered by weight, never in G steps per EC.
+ *   a == NULL  rows are ECs in the original EC order: id = ec_id, n_rows = E
+ *   a != NULL  rows are the (read id, EC) pairs of a in the stable sort by read id, the rows of msw_core_assign_table_*:
+ *              id = the read id, n_rows = the aligned reads.  Classes resident on h's device are read where they lie, any
+ *              other handle's host arrays are uploaded.
+ * Within a row the lines are in ascending g; a row without a kept cell gives no bytes; two calls give the same bytes.
+ *   msw_core_sparse_probs_begin      selects (replaces an earlier selection); *n_rows_out: the rows
+ *   msw_core_sparse_probs_next       the next whole rows whose text fits max_bytes (1 ... 1 GiB), in the handle's pinned text
+ *                                    buffer (valid until the next text call); *rows_done_out: the rows handed out so far;
+ *                                    *len_out == 0 with *rows_done_out == n_rows: finished.  *n_cells_out: the kept cells of
+ *                                    the piece, *n_host_cells_out: those the host printed.  A single row larger than
+ *                                    max_bytes is an error naming its size (a row is measured with its undecided cells 13
+ *                                    bytes wide, as the device writes them); the selection stays where it was.
+ *   msw_core_sparse_probs_next_gzip  the same inside the handle's open gzip stream (msw_core_gzip_begin ... _end), as
+ *                                    msw_fastq_next_gzip: the bytes to append to the file; *text_len_out: the plain length
+ *   msw_core_last_sparse_probs_timing  measurement hook (tools/sparse_probs_timing.py): device time of the kernels since
+ *                                    begin (events on the handle's stream; copies and the gzip kernels are not in it), the
+ *                                    bytes of text handed out and the kept cells
+ * Device memory O(E + pairs + the candidates and text of a piece), never G x E; an allocation that fails is an error
+ * naming the bytes.  The kept state is dropped by a new resident likelihood (set_*, build_*), a solve, a bootstrap and
+ * msw_core_trim.  Refused (non-zero, msw_last_error, the handle stays usable): no solve yet, a threshold that is NaN,
+ * <= 0 or > 1, an alignment whose EC count is not the handle's E, the dense flavour (MSWEEP_DENSE_COMPRESS=0), a
+ * communicator set, next without begin, the gzip variant without an open stream. */
+int msw_core_sparse_probs_begin(msw_handle h, struct msw_alignment *a, double threshold, uint64_t *n_rows_out,
+                                double *log_thr_out);
+int msw_core_sparse_probs_next(msw_handle h, size_t max_bytes, const char **text_out, size_t *len_out,
+                               uint64_t *rows_done_out, uint64_t *n_cells_out, size_t *n_host_cells_out);
+int msw_core_sparse_probs_next_gzip(msw_handle h, size_t max_bytes, const char **out, size_t *len_out,
+                                    uint64_t *rows_done_out, size_t *text_len_out);
+int msw_core_last_sparse_probs_timing(msw_handle h, double *kernel_ms_out, uint64_t *bytes_out, uint64_t *cells_out);
+
 /* The text of the matrix outputs, formatted on the device (text_kernels.hpp): the lines of the ECs [ec_begin, ec_end)
  * as contiguous bytes in EC order, every cell printed as the reference's default `ostream <<` prints a double --
  * printf("%g"), byte for byte (g6_format.hpp).  Only the bytes cross the link; nothing is sized G x E.

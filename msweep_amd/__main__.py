@@ -11,6 +11,9 @@ FASTQ file themselves, gathered on the device where the file lies (Core.fastq_op
 --write-unassigned / --write-assignment-table (with --bin-reads) add what `mGEMS bin` gives beyond the target bins:
 `<dir>/unassigned_reads.bin`, the aligned reads no estimated group claims, and `<prefix>_reads_to_groups.tsv`, a 0/1 column
 per target for every aligned read, formatted on the device (Core.assign_reads_aln / assign_table_block).
+--write-read-probs / --probs-threshold x writes the probabilities per READ and sparse: `<prefix>_read_probs.tsv`, one line
+`read id, group, probability` per aligned read and group at or above x, selected and formatted on the device
+(Core.sparse_probs; write_read_probs below, msweep_amd/read_probs.py).
 Every tab-separated column of the -i file is a grouping of its own: the estimation runs once per column
 (src/mSWEEP.cpp:282) from ONE read of the pseudoalignment, and the files are `<prefix>_<i>_...` when there are several.
 --samples FILE runs a whole manifest of samples (msweep_amd/samples.py) in this one process: -i is read once, every worker
@@ -28,7 +31,7 @@ import threading
 
 import numpy as np
 
-from . import binning, nested, parallel, samples
+from . import binning, nested, parallel, read_probs, samples
 from .core import ALGO_EM, ALGO_RCG, PREC_DOUBLE, PREC_FLOAT, TEXT_BITSEQ, TEXT_LOGL, TEXT_PROBS, Core, MswError
 from .likelihood import from_device_alignment, from_likelihood_file, read_likelihood_file  # noqa: F401 (read_likelihood_file: the host parser, under its name here)
 from .reference import Grouping, _split, output_path, read_references
@@ -72,6 +75,10 @@ def parse(argv):
                     help="with --bin-reads: <dir>/unassigned_reads.bin, the aligned reads no estimated group claims")
     ap.add_argument("--write-assignment-table", action="store_true",
                     help="with --bin-reads: <prefix>_reads_to_groups.tsv, a 0/1 column per target group for every aligned read")
+    ap.add_argument("--write-read-probs", action="store_true",
+                    help="<prefix>_read_probs.tsv: one line `read id, group, probability` per aligned read and group at or above "
+                         "--probs-threshold, written on the device")
+    ap.add_argument("--probs-threshold", help="with --write-read-probs: a probability in (0, 1] (default 0.001)")
     ap.add_argument("--compress", default="plaintext", help="plaintext or z (gzip, written on the device)")
     ap.add_argument("--compression-level", type=int, default=6, help="0 stores; 1 ... 9 run the same parse")
     ap.add_argument("--device", type=int, default=0)
@@ -334,6 +341,23 @@ def extract_reads(core, aln, targets, bin_ptr, reads, a, n_reads=None):
         _say(a, f"Extracting the reads failed:\n  {ex}\nexiting\n")
         return 1
     return 0
+
+
+def write_read_probs(core, aln, path, names, a, note=""):
+    """--write-read-probs: the header (msweep_amd/read_probs.py), then the rows the device selects and formats
+    (Core.sparse_probs by read: one line per aligned read and group with probability >= --probs-threshold), a piece of
+    read_probs.PIECE bytes at a time: only bytes come to the host."""
+    with _open_out(core, path, a) as f:
+        f.write(read_probs.header(a.probs_tau, names))
+        sp = core.sparse_probs(aln, a.probs_tau)
+        if isinstance(f, GzipOut):
+            f.pieces(sp.pieces_gzip(read_probs.PIECE))
+        else:
+            for piece in sp.pieces(read_probs.PIECE):
+                f.write(piece)
+        if a.verbose:
+            _, nbytes, cells = sp.last_timing()
+            _say(a, f"note: {note}read probabilities: {sp.rows} rows, {cells} cells at or above {a.probs_tau:g}, {nbytes} bytes\n")
 
 
 def write_assignment_table(core, path, targets, a):
@@ -653,6 +677,13 @@ def main(argv=None):
         if any(not p for p in a.extract_reads):
             sys.stderr.write("Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n")
             return 1
+    try:
+        # --write-read-probs / --probs-threshold (msweep_amd/read_probs.py)
+        a.probs_tau = read_probs.check_flags(a.write_read_probs, a.probs_threshold, bool(a.prefix), manifest is not None,
+                                             bool(a.read_likelihood), a.no_fit_model, a.nested)
+    except read_probs.ReadProbsError as ex:
+        sys.stderr.write(f"Parsing arguments failed:\n  {ex}\nexiting\n")
+        return 1
     if a.nested:
         # --nested: the flags it refuses and the tree of -i are judged before the GPU is touched (msweep_amd/nested.py)
         given = [f for f, v in (("--read-likelihood", a.read_likelihood), ("--no-fit-model", a.no_fit_model), ("--alphas", a.alphas),
@@ -788,6 +819,14 @@ def run_grouping(a, core, aln, grouping, index, K, algo, prec, node=None):
         rc = bin_reads(core, aln, est, res["theta"], a, path("reads_to_groups.tsv"), note, node)
         if rc:
             return rc
+    if a.write_read_probs:
+        # from the point estimate, before the replicates (a bootstrap drops the selection the device keeps)
+        try:
+            write_read_probs(core, aln, path("read_probs.tsv"), [n for n, m in zip(grouping.get_names(), lik.groups_considered()) if m],
+                             a, note)
+        except (MswError, RuntimeError, OSError) as ex:
+            _say(a, f"Writing the read probabilities failed:\n  {ex}\nexiting\n")
+            return 1
     try:
         if a.iters > 0:
             if a.seed == 26012023:      # the reference's "random seed" sentinel (src/BootstrapSample.cpp:48-50)

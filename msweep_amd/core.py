@@ -40,6 +40,8 @@ EXPORTS = [
     "msw_core_set_option", "msw_core_get_option", "msw_core_bin_reads", "msw_core_bin_reads_aln",
     "msw_core_assign_reads", "msw_core_assign_reads_aln", "msw_core_assign_table_rows", "msw_core_assign_table_block",
     "msw_core_assign_table_block_gzip",
+    "msw_core_sparse_probs_begin", "msw_core_sparse_probs_next", "msw_core_sparse_probs_next_gzip",
+    "msw_core_last_sparse_probs_timing",
     "msw_core_text_block", "msw_core_format_g6", "msw_core_last_text_timing",
     "msw_core_gzip_begin", "msw_core_text_block_gzip", "msw_core_gzip_append", "msw_core_gzip_end", "msw_core_last_gzip_timing",
     "msw_core_inflate_gzip", "msw_alignment_last_inflate", "msw_alignment_subset",
@@ -193,6 +195,11 @@ def load_library():
     L.msw_core_last_gzip_timing.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.msw_core_inflate_gzip.argtypes = [vp, vp, sz, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(InflateInfo)]
     L.msw_alignment_last_inflate.argtypes = [vp, C.POINTER(InflateInfo), sz, C.POINTER(sz)]
+    L.msw_core_sparse_probs_begin.argtypes = [vp, vp, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    L.msw_core_sparse_probs_next.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(sz)]
+    L.msw_core_sparse_probs_next_gzip.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(sz)]
+    L.msw_core_last_sparse_probs_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.msw_fastq_open.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(FastqInfo)]
     L.msw_fastq_select.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.msw_fastq_next.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz)]
@@ -437,6 +444,49 @@ class Fastq:
 
     def __exit__(self, *a):
         self.close()
+
+
+class SparseProbs:
+    """The selection msw_core_sparse_probs_begin left on a Core: the cells with probability >= threshold as lines
+    "id\tg\tp\n", rows by EC or by aligned read.  .rows, .log_threshold; the text in pieces of whole rows -- plain bytes, or
+    bytes of the Core's open gzip stream.  A new likelihood, a solve, a bootstrap or Core.trim() ends it."""
+
+    def __init__(self, core, rows, log_threshold):
+        self._core, self.rows, self.log_threshold = core, rows, log_threshold
+        self.cells = self.host_cells = 0    # kept cells / cells the host printed, over the pieces taken so far
+
+    def pieces(self, max_bytes=256 << 20):
+        """The text of the next whole rows, at most max_bytes per piece (msw_core_sparse_probs_next)."""
+        c = self._core
+        while True:
+            p, n, done, nc, nh = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_uint64(), C.c_size_t()
+            c._check(c._L.msw_core_sparse_probs_next(c._h, int(max_bytes), C.byref(p), C.byref(n), C.byref(done), C.byref(nc),
+                                                     C.byref(nh)))
+            self.cells += nc.value
+            self.host_cells += nh.value
+            if n.value:
+                yield C.string_at(p.value, n.value)
+            if done.value >= self.rows:
+                return
+
+    def pieces_gzip(self, max_bytes=256 << 20):
+        """The same inside the Core's open gzip stream (msw_core_sparse_probs_next_gzip): per piece the bytes to append to
+        the file (zlib on the host, MSWEEP_HOST_GZIP=1, may hold a piece's bytes back: b"")."""
+        c = self._core
+        while True:
+            p, n, done, nt = C.c_void_p(), C.c_size_t(), C.c_uint64(), C.c_size_t()
+            c._check(c._L.msw_core_sparse_probs_next_gzip(c._h, int(max_bytes), C.byref(p), C.byref(n), C.byref(done), C.byref(nt)))
+            if nt.value:
+                yield C.string_at(p.value, n.value) if n.value else b""
+            if done.value >= self.rows:
+                return
+
+    def last_timing(self):
+        """(ms of the kernels since begin -- device events --, text bytes they wrote, kept cells)"""
+        c = self._core
+        ms, nb, nc = C.c_double(), C.c_uint64(), C.c_uint64()
+        c._check(c._L.msw_core_last_sparse_probs_timing(c._h, C.byref(ms), C.byref(nb), C.byref(nc)))
+        return ms.value, nb.value, nc.value
 
 
 def _ptr(a):
@@ -876,6 +926,16 @@ class Core:
                                                              C.byref(nt)))
         out = C.string_at(p.value, n.value) if n.value else b""
         return (out, nt.value) if with_info else out
+
+    # ---- --write-read-probs: the probabilities at or above a threshold as sparse text (msw_core_sparse_probs_*)
+    def sparse_probs(self, aln, threshold):
+        """Selects the cells with gamma(g, j) >= log(threshold) of the last solve (msw_core_sparse_probs_begin): rows are
+        ECs when aln is None, else the aligned reads of the alignment in ascending id.  Returns a SparseProbs with .rows,
+        .log_threshold, .pieces(max_bytes), .pieces_gzip(max_bytes) and .last_timing()."""
+        n, lt = C.c_uint64(), C.c_double()
+        self._check(self._L.msw_core_sparse_probs_begin(self._h, aln._h if aln is not None else None, float(threshold),
+                                                        C.byref(n), C.byref(lt)))
+        return SparseProbs(self, n.value, lt.value)
 
     def set_trace_theta(self, n):
         self._check(self._L.msw_core_set_trace_theta(self._h, int(n)))

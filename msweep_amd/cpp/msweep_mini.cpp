@@ -18,6 +18,9 @@
 // --write-unassigned / --write-assignment-table (with --bin-reads): `<dir>/unassigned_reads.bin`, the aligned reads no
 // estimated group claims, and `<prefix>_reads_to_groups.tsv`, a 0/1 column per target for every aligned read, formatted on
 // the device (msw_core_assign_reads_aln, msw_core_assign_table_block).
+// --write-read-probs / --probs-threshold x: `<prefix>_read_probs.tsv`, one line `read id, group, probability` per aligned
+// read and group at or above x, selected and formatted on the device (msw_core_sparse_probs_*; DESIGN.md 7k;
+// tests/test_gpu_cli_read_probs.py).
 // Every tab-separated column of the -i file is a grouping of its own and the whole estimation runs once per column
 // (src/mSWEEP.cpp:282) -- from ONE read of the pseudoalignment, whose classes stay in device memory: run_grouping() is the
 // body of that loop, out_path() names its files (`<prefix>_<i>_...` when there are several; tests/test_gpu_groupings.py).
@@ -71,6 +74,10 @@ struct Args {
   std::vector<std::string> target_groups;
   double min_abundance = 0.0;
   bool write_unassigned = false, write_assignment_table = false;  // with --bin-reads: the unassigned bin, the table
+  // --write-read-probs / --probs-threshold x: <prefix>_read_probs.tsv, the probabilities at or above x per aligned read
+  bool write_read_probs = false, have_probs_threshold = false;
+  std::string probs_threshold;
+  double probs_tau = 0.001;
   bool have_extract_reads = false;
   std::vector<std::string> extract_reads;  // --extract-reads A[,B,...]: the FASTQ files the bins are extracted from
   std::string compress = "plaintext";  // or "z"
@@ -158,6 +165,11 @@ Args parse(int argc, char **argv) {
     else if (k == "--bin-reads") a.bin_reads = true;
     else if (k == "--write-unassigned") a.write_unassigned = true;
     else if (k == "--write-assignment-table") a.write_assignment_table = true;
+    else if (k == "--write-read-probs") a.write_read_probs = true;
+    else if (k == "--probs-threshold") {
+      a.probs_threshold = val();
+      a.have_probs_threshold = true;
+    }
     else if (k == "--compress") a.compress = val();
     else if (k == "--samples") {
       a.samples = val();
@@ -328,6 +340,18 @@ class Out {
     if (gz_) check(h_, msw_core_text_block_gzip(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr, nullptr));
     else check(h_, msw_core_text_block(h_, what, e0, e1, prefix, n_zero, &p, &n, nullptr));
     os_->write(p, (std::streamsize)n);
+  }
+  // the rows of the selection msw_core_sparse_probs_begin left, whole rows in pieces of at most max_bytes
+  void sparse_rows(uint64_t n_rows, size_t max_bytes) {
+    for (;;) {
+      const char *p = nullptr;
+      size_t n = 0;
+      uint64_t done = 0;
+      if (gz_) check(h_, msw_core_sparse_probs_next_gzip(h_, max_bytes, &p, &n, &done, nullptr));
+      else check(h_, msw_core_sparse_probs_next(h_, max_bytes, &p, &n, &done, nullptr, nullptr));
+      os_->write(p, (std::streamsize)n);
+      if (done >= n_rows) break;
+    }
   }
   // rows of the assignment table the handle keeps (msw_core_assign_table_block / _gzip)
   void table_block(size_t r0, size_t r1) {
@@ -569,6 +593,51 @@ void write_assignment_table(const Args &a, msw_handle h, const std::string &path
   for (size_t r0 = 0; r0 < n; r0 += block) f.table_block(r0, std::min(n, r0 + block));
   f.close();
   if (!f.good()) throw std::runtime_error("cannot write " + path);
+}
+
+// --write-read-probs / --probs-threshold: the refusals, in the words and the order of msweep_amd/read_probs.py; sets
+// a.probs_tau.  Throws what main() prints as `Parsing arguments failed`.
+void check_read_probs_flags(Args &a) {
+  if (a.have_probs_threshold) {
+    const std::string &t = a.probs_threshold;
+    char *end = nullptr;
+    double x = t.empty() || isspace((unsigned char)t[0]) ? NAN : strtod(t.c_str(), &end);
+    if ((end && *end) || t.find_first_of("xX_") != std::string::npos) x = NAN;  // (decimal text only, as Python's float())
+    if (!(x > 0.0 && x <= 1.0)) throw std::runtime_error("--probs-threshold must be a probability in (0, 1] (got " + t + ")");
+    a.probs_tau = x;
+    if (!a.write_read_probs) throw std::runtime_error("--probs-threshold needs --write-read-probs");
+  }
+  if (!a.write_read_probs) return;
+  if (a.prefix.empty() && !a.have_samples) throw std::runtime_error("--write-read-probs needs -o");
+  if (!a.read_likelihood.empty()) throw std::runtime_error("--write-read-probs can't be used with --read-likelihood");
+  if (a.no_fit_model) throw std::runtime_error("--write-read-probs can't be used with --no-fit-model");
+  if (a.nested) throw std::runtime_error("--write-read-probs can't be used with --nested");
+}
+
+// --write-read-probs: the header -- the threshold, one line per ESTIMATED group (g = its row in the resident likelihood, the
+// number the rows carry), the column names --, then the rows the device selects and formats, one line per aligned read and
+// group with probability >= --probs-threshold (msweep_amd/__main__.py write_read_probs: the same header, the same calls)
+void write_read_probs(const Args &a, msw_handle h, msw_alignment_t aln, const std::string &path, const std::vector<std::string> &est,
+                      const std::string &note) {
+  Out f(h, path, a.compress == "z", a.compression_level);
+  char num[64];
+  snprintf(num, sizeof num, "%.17g", a.probs_tau);
+  std::string head = std::string("#threshold\t") + num + "\n";
+  for (size_t g = 0; g < est.size(); ++g) head += "#group\t" + std::to_string(g) + "\t" + est[g] + "\n";
+  head += "#read_id\tgroup\tprob\n";
+  f.write(head);
+  uint64_t n_rows = 0;
+  check(h, msw_core_sparse_probs_begin(h, aln, a.probs_tau, &n_rows, nullptr));
+  f.sparse_rows(n_rows, (size_t)256 << 20);
+  f.close();
+  if (!f.good()) throw std::runtime_error("cannot write " + path);
+  if (a.verbose) {
+    uint64_t bytes = 0, cells = 0;
+    check(h, msw_core_last_sparse_probs_timing(h, nullptr, &bytes, &cells));
+    snprintf(num, sizeof num, "%g", a.probs_tau);
+    Msg() << "note: " << note << "read probabilities: " << n_rows << " rows, " << cells << " cells at or above " << num << ", "
+          << bytes << " bytes\n";
+  }
 }
 
 // the bins from the device and one file per target (an empty bin: an empty file), written on up to writer_threads()
@@ -945,6 +1014,15 @@ int run_grouping(const Args &a, const Run &r, const Grouping &grouping, size_t i
       // before the replicates and the probabilities (src/mSWEEP.cpp:437-469), from the point estimate
       if (bin_reads(a, h, r.aln, est_names, theta, r, path("reads_to_groups.tsv"), note, node) != 0) return 1;
     }
+    if (a.write_read_probs) {
+      // from the point estimate, before the replicates (a bootstrap drops the selection the device keeps)
+      try {
+        write_read_probs(a, h, r.aln, path("read_probs.tsv"), est_names, note);
+      } catch (const std::exception &ex) {
+        Msg() << "Writing the read probabilities failed:\n  " << ex.what() << "\nexiting\n";
+        return 1;
+      }
+    }
     if (a.iters > 0) {
       // every grouping's bootstrap starts the stream from the same seed (the reference constructs the sample inside its
       // loop); the random-seed sentinel draws anew per grouping
@@ -1293,6 +1371,12 @@ int main(int argc, char **argv) {
         std::cerr << "Extracting the reads failed:\n  --extract-reads has an empty path in its list\nexiting\n";
         return 1;
       }
+  }
+  try {
+    check_read_probs_flags(a);
+  } catch (const std::exception &ex) {
+    std::cerr << "Parsing arguments failed:\n  " << ex.what() << "\nexiting\n";
+    return 1;
   }
   if (a.nested) {
     // --nested: the flags it refuses and the tree of -i are judged before the GPU is touched (nested_tree.hpp)

@@ -278,6 +278,41 @@ struct AssignState {
   }
 };
 
+// ---- what msw_core_sparse_probs_begin keeps for msw_core_sparse_probs_next* (host_sparse_probs.inc).  Dropped by a new
+// likelihood, a solve, a bootstrap and msw_core_trim ----------------------------------------------------------------------
+struct SparseProbsState {
+  bool have = false;
+  uint64_t n_rows = 0, cur = 0;  // rows (ECs, or aligned reads); the next row to hand out
+  double log_thr = 0.0, a = 1.0, tref = 0.0;
+  const double *u = nullptr;     // the solver's u (a solve drops this state)
+  DevBuf<uint32_t> order;        // [G] the groups by u descending ...
+  DevBuf<double> us, lse_p;      // ... their u; [E] the normaliser at every permuted position
+  DevBuf<uint32_t> id, ec;       // by read: [n_rows] read id and EC of every row, ascending id (stable); by EC: none
+  DevBuf<uint64_t> coff, koff;   // [n_rows + 1] exclusive scans of the rows' candidates and kept cells
+  // a piece: candidates as written and sorted, their gamma, line lengths and offsets, the text
+  DevBuf<uint64_t> key, key2, eoff, pbits, span;
+  DevBuf<uint32_t> idx, idx2, elen, n_list;
+  DevBuf<double> gam;
+  DevBuf<uint8_t> text, closed, tmp;
+  DevBuf<TextHostCell> list;
+  DevBuf<TextFilledCell> cells;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double kernel_ms = 0.0;  // since begin (msw_core_last_sparse_probs_timing)
+  uint64_t bytes = 0, n_cells = 0;
+  void drop() {
+    have = false;
+    u = nullptr;
+    order.release(); us.release(); lse_p.release(); id.release(); ec.release(); coff.release(); koff.release();
+    key.release(); key2.release(); eoff.release(); pbits.release(); span.release(); idx.release(); idx2.release();
+    elen.release(); n_list.release(); gam.release(); text.release(); closed.release(); tmp.release(); list.release();
+    cells.release();
+  }
+  ~SparseProbsState() {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct msw_core {
   int device = 0;
   int n_cu = 256;
@@ -299,6 +334,9 @@ struct msw_core {
   InflateState inf;
   FastqState fastq;
   AssignState assign;
+  SparseProbsState sparse;
+  // what an earlier call kept of the solve before (host_assign.inc, host_sparse_probs.inc)
+  void drop_kept() { assign.drop(); sparse.drop(); }
   std::vector<uint64_t> lik_counts;  // first column of the last served likelihood file (host_likelihood_file.inc)
   Solver solver{&comm, &in_collective};  // on the handle's stream
 

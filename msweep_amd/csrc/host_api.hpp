@@ -10,6 +10,21 @@
 namespace msw {
 namespace host __attribute__((visibility("hidden"))) {
 
+// room for `count` elements in b (kept when it has them already): a failure is "<who>: cannot allocate <bytes> bytes of
+// device memory for <what>", the wording of every entry whose device memory grows with its input
+template <class T>
+void named_alloc(DevBuf<T> &b, size_t count, const char *who, const char *what) {
+  if (b.p && count <= b.n) return;
+  b.release();
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  if (hipMalloc((void **)&b.p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    throw Fail(std::string(who) + ": cannot allocate " + std::to_string(bytes) + " bytes of device memory for " + what);
+  }
+  b.n = std::max<size_t>(count, 1);
+}
+
 extern thread_local std::string g_create_error;  // msweep_core.hip: msw_last_error(null), msw_comm_last_error
 // msweep_core.hip: the dynamic-LDS limit of `kernel` on the current device becomes at least `bytes` (lds_grants.hpp: one
 // table for all handles, limits only rise)
@@ -41,6 +56,9 @@ void reset_likelihood(msw_core *h);  // host_likelihood.inc
 void dense_from_stage(msw_core *h, const double *Lm, size_t ld, const double *stage, size_t G, size_t E);
 void materialise_args(msw_core *h, bool gamma, MaterialiseArgs &m);
 void materialise_block(msw_core *h, const MaterialiseArgs &m, bool gamma, size_t j0, size_t j1, double *buf);
+// host_assign.inc: the (read id, EC) pairs of device-resident classes in a stable sort by id (k_assign_expand, a radix sort)
+void reads_by_id(msw_core *h, const uint64_t *d_rptr, const uint32_t *d_reads, uint32_t E, uint64_t n_rows,
+                 DevBuf<uint32_t> &id, DevBuf<uint32_t> &ec, const char *who);
 
 // ---- input.hip ---------------------------------------------------------------------------------------------------
 void lik_gather_launch(hipStream_t st, const double *src, const uint64_t *idx, uint32_t n, double *out);  // k_lik_gather

@@ -11,15 +11,7 @@ constexpr size_t kAssignMaxBytes = (size_t)1 << 30;  // worst-case text of one t
 
 template <class T>
 void assign_alloc(DevBuf<T> &b, size_t count, const char *what) {
-  if (b.p && count <= b.n) return;
-  b.release();
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (hipMalloc((void **)&b.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    throw Fail("msw_core_assign_reads: cannot allocate " + std::to_string(bytes) + " bytes of device memory for " + what);
-  }
-  b.n = std::max<size_t>(count, 1);
+  named_alloc(b, count, "msw_core_assign_reads", what);
 }
 
 struct AssignPassArgs {
@@ -50,6 +42,33 @@ void launch_assign_enc(msw_core *h, const GammaState &gs, const AssignGroups &A,
   else if (L.hybrid()) launch_assign_passes<kEncIndex, LDS>(h, gs, A, P, write);
   else launch_assign_passes<kEncNarrow, LDS>(h, gs, A, P, write);
 }
+
+}  // namespace
+
+// The index of the (read id, EC) pairs by id: id[i], ec[i] = the i-th pair in the stable sort by read id -- the rows of the
+// assignment table, and of msw_core_sparse_probs_* by read (host_sparse_probs.inc).  rptr / reads: device memory.
+void msw::host::reads_by_id(msw_core *h, const uint64_t *d_rptr, const uint32_t *d_reads, uint32_t E, uint64_t n_rows,
+                            DevBuf<uint32_t> &id, DevBuf<uint32_t> &ec, const char *who) {
+  if (!n_rows) return;
+  hipStream_t st = h->stream;
+  auto alloc = [&](auto &b, size_t count, const char *what) { named_alloc(b, count, who, what); };
+  DevBuf<uint32_t> id0, ec0;
+  DevBuf<uint8_t> tmp;
+  alloc(id0, n_rows, "the read positions");
+  alloc(ec0, n_rows, "the read positions");
+  alloc(id, n_rows, "the reads by id");
+  alloc(ec, n_rows, "the reads by id");
+  const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + 255) / 256, (uint64_t)h->n_cu * 16));
+  hipLaunchKernelGGL(k_assign_expand, dim3(nb), dim3(256), 0, st, d_rptr, d_reads, E, n_rows, id0.p, ec0.p);
+  MSW_HIP(hipGetLastError());
+  size_t tmp_bytes = 0;
+  MSW_HIP(prim_sort_pairs(nullptr, tmp_bytes, id0.p, id.p, ec0.p, ec.p, (size_t)n_rows, 32u, st));
+  alloc(tmp, tmp_bytes, "sort storage");
+  MSW_HIP(prim_sort_pairs(tmp.p, tmp_bytes, id0.p, id.p, ec0.p, ec.p, (size_t)n_rows, 32u, st));
+  MSW_HIP(hipStreamSynchronize(st));
+}
+
+namespace {
 
 void assign_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads, size_t n_ecs, bool on_device,
                        const double *thresholds, const uint32_t *targets, size_t n_targets, unsigned flags, uint64_t *bin_ptr,
@@ -219,20 +238,7 @@ void assign_reads_impl(msw_core *h, const uint64_t *rptr, const uint32_t *reads,
   if (!keep) return;
 
   // the reads by id: (read id, EC) of every read position, in a stable sort by id
-  if (n_rows) {
-    DevBuf<uint32_t> id0, ec0;
-    assign_alloc(id0, n_rows, "the read positions");
-    assign_alloc(ec0, n_rows, "the read positions");
-    assign_alloc(K.id, n_rows, "the reads by id");
-    assign_alloc(K.ec, n_rows, "the reads by id");
-    const unsigned nb = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + 255) / 256, (uint64_t)h->n_cu * 16));
-    hipLaunchKernelGGL(k_assign_expand, dim3(nb), dim3(256), 0, st, d_rptr, d_reads, E, n_rows, id0.p, ec0.p);
-    MSW_HIP(hipGetLastError());
-    MSW_HIP(prim_sort_pairs(nullptr, tmp_bytes, id0.p, K.id.p, ec0.p, K.ec.p, (size_t)n_rows, 32u, st));
-    assign_alloc(tmp, tmp_bytes, "sort storage");
-    MSW_HIP(prim_sort_pairs(tmp.p, tmp_bytes, id0.p, K.id.p, ec0.p, K.ec.p, (size_t)n_rows, 32u, st));
-    MSW_HIP(hipStreamSynchronize(st));
-  }
+  reads_by_id(h, d_rptr, d_reads, E, n_rows, K.id, K.ec, "msw_core_assign_reads");
   K.n_rows = n_rows;
   K.n_targets = (uint32_t)n_targets;
   K.have = true;

@@ -8,15 +8,7 @@ namespace {
 // hipMalloc that names what failed and how many bytes it wanted (an out-of-memory result is an error, never a fault)
 template <class T>
 void bin_alloc(DevBuf<T> &b, size_t count, const char *what) {
-  if (b.p && count <= b.n) return;
-  b.release();
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (hipMalloc((void **)&b.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    throw Fail("msw_core_bin_reads: cannot allocate " + std::to_string(bytes) + " bytes of device memory for " + what);
-  }
-  b.n = std::max<size_t>(count, 1);
+  named_alloc(b, count, "msw_core_bin_reads", what);
 }
 
 template <int ENC, bool LDS>

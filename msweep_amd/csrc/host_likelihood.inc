@@ -15,7 +15,7 @@ void msw::host::reset_likelihood(msw_core *h) {
   h->solver.have_solution = false;
   h->solver.prepared = false;
   h->iperm.release();
-  h->assign.drop();
+  h->drop_kept();
   L.long_row = multilane() ? kLongRow : kLongRowOneLane;
   if (const char *lr = getenv("MSWEEP_LONG_ROW"))  // developer switch
     L.long_row = (uint32_t)std::min(std::max(atoi(lr), 16), (int)L.long_row);

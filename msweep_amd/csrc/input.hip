@@ -48,6 +48,7 @@ int msw_core_trim(msw_handle h) {
     h->reader_pool.trim();
     h->text.release_device();  // (the pinned text of the last msw_core_text_block stays valid)
     h->gz.release_device();
+    h->sparse.drop();  // (msw_core_sparse_probs_begin's selection: device memory throughout)
   });
 }
 

@@ -36,7 +36,7 @@ int msw_core_solve(msw_handle h, const double *logc, const double *alpha0, doubl
                    int algo, int prec, double *theta_out, size_t *iters_out, double *bound_out) {
   return guarded(h, [&] {
     if (!alpha0) throw Fail("msw_core_solve: null alpha0");
-    h->assign.drop();  // (the kept assignment table belongs to the solve before: host_assign.inc)
+    h->drop_kept();  // (the kept assignment table belongs to the solve before: host_assign.inc)
     prepare_inputs(h->lik, h->solver, logc, nullptr, alpha0);
     run_impl(h->lik, h->solver, tol, max_iters, algo, prec, theta_out, iters_out, bound_out);
   });
@@ -45,7 +45,7 @@ int msw_core_solve(msw_handle h, const double *logc, const double *alpha0, doubl
 int msw_core_prepare(msw_handle h, const double *logc, const double *alpha0) {
   return guarded(h, [&] {
     if (!alpha0) throw Fail("msw_core_prepare: null alpha0");
-    h->assign.drop();
+    h->drop_kept();
     prepare_inputs(h->lik, h->solver, logc, nullptr, alpha0);
   });
 }
@@ -53,14 +53,14 @@ int msw_core_prepare(msw_handle h, const double *logc, const double *alpha0) {
 int msw_core_run(msw_handle h, double tol, size_t max_iters, int algo, int prec, double *theta_out,
                  size_t *iters_out, double *bound_out) {
   return guarded(h, [&] {
-    h->assign.drop();
+    h->drop_kept();
     run_impl(h->lik, h->solver, tol, max_iters, algo, prec, theta_out, iters_out, bound_out);
   });
 }
 
 int msw_core_continue(msw_handle h, size_t n_iters, double *theta_out, size_t *iters_out, double *bound_out) {
   return guarded(h, [&] {
-    h->assign.drop();
+    h->drop_kept();
     continue_impl(h->lik, h->solver, n_iters, theta_out, iters_out, bound_out);
   });
 }
@@ -94,7 +94,7 @@ int msw_core_bootstrap(msw_handle h, const uint32_t *ec_counts, int32_t seed, si
                        size_t rep_begin, size_t rep_end, const double *alpha0, double tol,
                        size_t max_iters, int algo, int prec, double *theta_out, size_t *iters_out) {
   return guarded(h, [&] {
-    h->assign.drop();
+    h->drop_kept();
     bootstrap_impl(h, ec_counts, seed, bootstrap_count, rep_begin, rep_end, alpha0, tol, max_iters,
                    algo, prec, theta_out, iters_out);
   });
@@ -114,7 +114,7 @@ int msw_core_bootstrap_dist(msw_handle h, msw_comm_t comm, const uint32_t *ec_co
   // (a rank whose block fails still joins the all-gather and reports through its status word: every rank
   // returns non-zero, none is left waiting, and the communicator stays usable -- host_bootstrap.inc)
   return guarded(h, [&] {
-    h->assign.drop();
+    h->drop_kept();
     bootstrap_dist_impl(h, comm, ec_counts, seed, bootstrap_count, n_replicates, alpha0, tol, max_iters, algo,
                         prec, theta_out, iters_out);
   });
